@@ -10,6 +10,13 @@ per-GPU table size fixed).
 
 value = canonical field ops / s of the whole job = 32 * (2^n - 1) * steps / time
 (SURVEY.md 8(d)); ms_per_step = prover milliseconds per proof.
+
+A plain run does only what that headline needs: set-up, the first proof
+(checked against its fixture), the warm-up, the timed steps, the result line.
+--full adds every side leg (config 4, serving, host tables, fold, circuit,
+config 5 + KZG, config 1 + plain prove, CPU baselines, the N > 1 peer leg);
+the --no-* switches then drop single legs. --dump-outputs DIR writes the last
+timed proof as .npy files, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -38,6 +45,14 @@ def parse():
     ap.add_argument("--nvars", type=int, default=24, help="variables per GPU")
     ap.add_argument("--field", default="bn254_fr", choices=sorted(FIELDS))
     ap.add_argument("--seed", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side legs (config 4, serving, host tables, fold, circuit, config 5 + KZG, "
+                    "config 1 + plain prove, CPU baselines, the N>1 peer-reduction leg); the --no-* switches below "
+                    "drop single legs of a --full run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last timed proof (what the prover call returned: round "
+                    "polynomial coefficients, their counts, challenges) to DIR/<name>.npy as float64 arrays of "
+                    "32-bit words (exact)")
     ap.add_argument("--cpu-sample-nvars", type=int, default=24,
                     help="size of the single-thread reference-faithful CPU run (24 = the headline workload)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -62,7 +77,10 @@ def parse():
     ap.add_argument("--no-events", action="store_true", help="diagnostic: time without per-launch HIP events")
     ap.add_argument("--no-plain", action="store_true",
                     help="skip BASELINE config 1 (12-var plain prove, CPU port) and the GPU plain prove/verify legs")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0 (ms_per_step is the time of the --steps timed proofs)")
+    return args
 
 
 def golden_key(field: int, n: int, seed: int) -> str:
@@ -98,6 +116,20 @@ def proof_digest_check(field: int, n: int, seed: int, polys, chal, abort: bool =
     if abort and fix and dig != fix["blob_keccak256"]:
         raise SystemExit(f"proof digest {dig} != oracle fixture {fix['blob_keccak256']} ({key})")
     return out
+
+
+def dump_outputs(path: str, coeffs, nco, ch) -> None:
+    """--dump-outputs: the arrays the timed prover call filled in its last
+    step, as float64 .npy files. The u64 limb arrays are written as their
+    little-endian 32-bit words (a float64 holds each exactly): coeffs
+    uint64[n, 3, 4] -> [n, 3, 8], challenges uint64[n, 4] -> [n, 8]. The tables
+    are seeded (--seed), so the same arguments give the same files."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "round_poly_coeffs.npy"), coeffs.view("<u4").astype(np.float64))
+    np.save(os.path.join(path, "round_poly_ncoeffs.npy"), nco.astype(np.float64))
+    np.save(os.path.join(path, "challenges.npy"), ch.view("<u4").astype(np.float64))
 
 
 def kzg_commit_check(nvars: int, out) -> dict:
@@ -915,6 +947,8 @@ def main() -> None:
         ranks = [None] * world
         dist.all_gather_object(ranks, mine)
     assert np.array_equal(first_challenges, ch), "proof changed between steps"
+    if args.dump_outputs and rank == 0:  # (every rank holds the same proof)
+        dump_outputs(args.dump_outputs, coeffs, nco, ch)
 
     ops = 32.0 * ((1 << n) - 1) * args.steps
     value = ops / elapsed
@@ -976,9 +1010,9 @@ def main() -> None:
         if t.get("kind") == dom and field == 0:  # the longest launch of this workload
             traffic = t["traffic_bytes_per_launch"]  # HBM bytes per launch, beside alg_bytes_per_launch
             traffic_src = f"profiles/{os.path.basename(tpath)} ({t['method']}); traffic/alg = {t['traffic_over_alg']:.4f}"
-    cfg4 = config4_bench(ctx, field, world, rank, barrier) if args.config4 else None
+    cfg4 = config4_bench(ctx, field, world, rank, barrier) if args.full and args.config4 else None
     peer_leg = None
-    if world > 1 and args.reduce == "comm" and not args.no_peer_leg:
+    if args.full and world > 1 and args.reduce == "comm" and not args.no_peer_leg:
         # the headline again with --reduce peer, in N fresh ranks that rank 0
         # starts as child processes (one per GPU): a failure or hang there can
         # only cost the side field, never this line
@@ -1082,27 +1116,28 @@ def main() -> None:
                 "collective_us_each_rank0": [round(x["ms"] * 1e3, 2) for x in colls],
                 "ranks": ranks,
             }
+        side = args.full and world == 1  # the one-GPU side legs: --full only
         if cfg4 is not None:
             out["config4_26var"] = cfg4
         if peer_leg is not None:
             out["peer_reduce_leg"] = peer_leg
-        if not args.no_serving and world == 1:
+        if not args.no_serving and side:
             out["serving_2_streams"] = serving_bench(field, tabs, n, first_challenges)
-        if not args.no_e2e and world == 1:
+        if not args.no_e2e and side:
             e2e = e2e_bench(ctx, field, tabs, n)
             e2e["same_proof_as_device_resident"] = bool(np.array_equal(e2e.pop("challenges"), ch))
             out["e2e_host_tables"] = e2e
-        if not args.no_fold and world == 1:
+        if not args.no_fold and side:
             out["fold_20var"] = fold_bench(ctx, field)
-        if not args.no_circuit and world == 1:
+        if not args.no_circuit and side:
             out["gkr_circuit"] = circuit_bench(ctx, field)
-        if not args.no_config5 and world == 1:
+        if not args.no_config5 and side:
             out["config5_bls12_381"] = config5_bench(ctx)
             out["gkr_circuit_kzg"] = circuit_kzg_bench(ctx)
-        if not args.no_plain and world == 1:
+        if not args.no_plain and side:
             out["config1_12var_prove"] = config1_bench(ctx, field)
             out["plain_sumcheck"] = [plain_bench(ctx, field, nv) for nv in (20, 24)]
-        if world == 1 and not args.no_cpu_baseline:
+        if side and not args.no_cpu_baseline:
             cb = cpu_baseline(field, args.cpu_sample_nvars, args.cpu_fast_nvars)
             out["cpu_baseline"] = cb
             out["speedup_vs_cpu_baseline"] = value / cb["value"]

@@ -8,7 +8,7 @@
 #   tests=EXPR       -m gpu tests selected by pytest -k EXPR
 #   file=PATH        one GPU test file
 #   smoke            __graft_entry__.smoke()
-#   bench            the default bench line (what the driver runs)
+#   bench            the bench line with every side leg (bench.py --full)
 #   quick            headline proof only (no side legs), 100 steps
 #   c4               headline + config 4 only
 #   self2            `python bench.py --gpus 2 --comm host` (self-launched ranks on one card)
@@ -77,22 +77,22 @@ for step in "$@"; do
       timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $log 2>&1 || fail $step $? $log
       tail -1 $log ;;
     bench)
-      timeout -k 10 600 python bench.py > gpurun_out/bench.json 2> gpurun_out/bench.err || fail $step $? gpurun_out/bench.err
+      timeout -k 10 600 python bench.py --full > ${log%.log}.json 2> ${log%.log}.err || fail $step $? ${log%.log}.err
       summ gpurun_out/bench.json ;;
     quick)
       timeout -k 10 300 python bench.py $SIDE --no-config4 > gpurun_out/quick.json 2> gpurun_out/quick.err || fail $step $? gpurun_out/quick.err
       summ gpurun_out/quick.json ;;
     c4)
-      timeout -k 10 300 python bench.py $SIDE > gpurun_out/c4.json 2> gpurun_out/c4.err || fail $step $? gpurun_out/c4.err
+      timeout -k 10 300 python bench.py --full $SIDE > ${log%.log}.json 2> ${log%.log}.err || fail $step $? ${log%.log}.err
       summ gpurun_out/c4.json ;;
     self2)
-      env -u WORLD_SIZE -u RANK -u LOCAL_RANK timeout -k 10 600 python bench.py --gpus 2 --comm host --steps 10 --warmup 3 $SIDE > gpurun_out/self2.json 2> gpurun_out/self2.err || fail $step $? gpurun_out/self2.err
+      env -u WORLD_SIZE -u RANK -u LOCAL_RANK timeout -k 10 600 python bench.py --full --gpus 2 --comm host --steps 10 --warmup 3 $SIDE > ${log%.log}.json 2> ${log%.log}.err || fail $step $? ${log%.log}.err
       summ gpurun_out/self2.json ;;
     self8)
-      env -u WORLD_SIZE -u RANK -u LOCAL_RANK timeout -k 10 900 python bench.py --gpus 8 --comm host --steps 3 --warmup 1 $SIDE > gpurun_out/self8.json 2> gpurun_out/self8.err || fail $step $? gpurun_out/self8.err
+      env -u WORLD_SIZE -u RANK -u LOCAL_RANK timeout -k 10 900 python bench.py --full --gpus 8 --comm host --steps 3 --warmup 1 $SIDE > ${log%.log}.json 2> ${log%.log}.err || fail $step $? ${log%.log}.err
       summ gpurun_out/self8.json ;;
     rccl1)
-      timeout -k 10 300 python bench.py --force-rccl --steps 20 --warmup 5 $SIDE > gpurun_out/rccl1.json 2> gpurun_out/rccl1.err || fail $step $? gpurun_out/rccl1.err
+      timeout -k 10 300 python bench.py --full --force-rccl --steps 20 --warmup 5 $SIDE > ${log%.log}.json 2> ${log%.log}.err || fail $step $? ${log%.log}.err
       summ gpurun_out/rccl1.json ;;
     trace)
       ZK_DEBUG_TAIL=1 timeout -k 10 120 python3 bench.py --steps 3 --warmup 1 $SIDE --no-config4 --no-events > gpurun_out/trace.json 2> gpurun_out/trace.err || fail $step $? gpurun_out/trace.err
@@ -104,7 +104,7 @@ for step in "$@"; do
     profile)
       bash tools/profile_bench.sh "${arg:-r5}" || fail $step $? gpurun_out/prof_${arg:-r5}.err ;;
     kzg)
-      timeout -k 10 600 python bench.py --no-cpu-baseline --no-fold --no-e2e --no-serving --no-circuit --no-plain --no-config4 --steps 5 --warmup 2 > gpurun_out/kzg.json 2> gpurun_out/kzg.err || fail $step $? gpurun_out/kzg.err
+      timeout -k 10 600 python bench.py --full --no-cpu-baseline --no-fold --no-e2e --no-serving --no-circuit --no-plain --no-config4 --steps 5 --warmup 2 > ${log%.log}.json 2> ${log%.log}.err || fail $step $? ${log%.log}.err
       summ gpurun_out/kzg.json ;;
     mb)
       prog=${arg%%:*}
