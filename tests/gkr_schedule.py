@@ -1,6 +1,7 @@
 """The step schedule of a sharded GKR sum-check (test helper, not a test
 module): which rounds each device step covers and how many collectives a
-sharded proof makes, as host.hpp `gkr_phase` / `gkr_prove_device` build them.
+sharded proof makes, as gkr_plan.hpp `plan_phase` / host.hpp `gkr_prove_device`
+build them (tests/test_gkr_plan_cpu.py holds this helper to the shipped planner).
 Shared by tests/test_gpu_sharded.py (checks the library's collective count)
 and tests/test_dist_cpu.py (runs the same schedule over gloo on the CPU)."""
 from __future__ import annotations
@@ -8,7 +9,7 @@ from __future__ import annotations
 
 def bounds(nloc: int, d0: bool = True) -> list[int]:
     """End round of each step of a sharded phase (no persistent steps across
-    ranks), as host.hpp gkr_phase builds the schedule: n >= 11 — the input
+    ranks), as gkr_plan.hpp plan_phase builds the schedule: n >= 11 — the input
     pass over rounds 0-2, triple steps, one two-round step (dm3), double steps;
     smaller — round 0 (+ one or two single rounds) or rounds 0-1, then doubles."""
     b: list[int] = []

@@ -3,7 +3,8 @@ collective schedule.
 
 Each rank holds its low-index-bit shard of the four GKR tables (local m <->
 global m * world + rank) and runs the step schedule the device code runs
-(host.hpp gkr_phase / gkr_prove_device, tests/gkr_schedule.py):
+(gkr_plan.hpp plan_phase, host.hpp gkr_phase / gkr_prove_device,
+tests/gkr_schedule.py):
 
 * each step covers 1, 2 or 3 rounds and exchanges exactly what the device
   step publishes: round 0 alone — e0, e1, e2; a single round — e0, e2; a
@@ -13,7 +14,7 @@ global m * world + rank) and runs the step schedule the device code runs
   k_gkr_d0t / k_gkr_t33 tiles;
 * ONE limb-split u64 all-reduce per step (zk_amd.dist.TorchAllreduce, the host
   communicator the library calls back into), then every rank derives the
-  step's rounds with the host's formulas (three_rounds / two_rounds) from an
+  step's rounds with the host's formulas (gkr_rounds.hpp three_rounds / two_rounds) from an
   identical transcript;
 * at the first step boundary leaving <= ZK_GATHER_VARS local rounds every rank
   folds by the pending challenges, the folded tables of all ranks are gathered
@@ -36,6 +37,8 @@ import sys
 
 import pytest
 
+from gkr_step_sums import _step_sums
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SEED = 17
 
@@ -44,71 +47,6 @@ def _free_port() -> int:
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
         return s.getsockname()[1]
-
-
-def _corner(tab, idx_bits, nb, q):
-    """Element of a table at corner idx_bits (nb leading variables) of block q."""
-    L = len(tab)
-    return tab[idx_bits * (L >> nb) + q]
-
-
-def _grid(p, tab, nb, q, pt):
-    """The table's multilinear extension in its nb leading variables at grid
-    point pt (coordinates in {0, 1, 2}), block q."""
-    vals = {}
-    for c in range(1 << nb):
-        vals[c] = _corner(tab, c, nb, q)
-    # extend one axis at a time: X(2) = 2 X(1) - X(0)
-    for axis in range(nb):
-        sh = nb - 1 - axis
-        t = pt[axis]
-        nxt = {}
-        for c, v in vals.items():
-            if (c >> sh) & 1:
-                continue
-            x0, x1 = v, vals[c | (1 << sh)]
-            nxt[c] = x0 if t == 0 else x1 if t == 1 else (2 * x1 - x0) % p
-        vals = nxt
-    return vals[0]
-
-
-def _step_sums(p, tabs, nb, first):
-    """What one device step publishes, as field values (mod p)."""
-    A, S, M, P = tabs
-    nq = len(A) >> nb
-    if nb == 1:
-        pts = [(0,), (1,), (2,)] if first else [(0,), (2,)]
-    elif nb == 2:
-        # categories (kernels.hpp): 0 V00, 1 V22, 2 V01, 3 V02, 4 V10, 5 V20, 6 V21, 7 V12 (+ 8 V11 first)
-        pts = [(0, 0), (2, 2), (0, 1), (0, 2), (1, 0), (2, 0), (2, 1), (1, 2)] + ([(1, 1)] if first else [])
-    else:
-        pts = None
-    if pts is not None:
-        out = []
-        for pt in pts:
-            acc = 0
-            for q in range(nq):
-                acc += _grid(p, A, nb, q, pt) * _grid(p, S, nb, q, pt) + _grid(p, M, nb, q, pt) * _grid(p, P, nb, q, pt)
-            out.append(acc % p)
-        return out
-    # three rounds: 27 moment tiles, id 9 alpha + 3 beta + gamma; per axis
-    # moment 0 = X0 Y0, 1 = X1 Y1, 2 = X0 Y1 + X1 Y0 over the octant's corners
-    sel = {0: [(0, 0)], 1: [(1, 1)], 2: [(0, 1), (1, 0)]}
-    T = [0] * 27
-    for q in range(nq):
-        cx = [[_corner(X, c, 3, q) for c in range(8)] for X in (A, M)]
-        cy = [[_corner(Y, c, 3, q) for c in range(8)] for Y in (S, P)]
-        for a in range(3):
-            for b in range(3):
-                for g in range(3):
-                    acc = 0
-                    for ua, va in sel[a]:
-                        for ub, vb in sel[b]:
-                            for ug, vg in sel[g]:
-                                u, v = 4 * ua + 2 * ub + ug, 4 * va + 2 * vb + vg
-                                acc += cx[0][u] * cy[0][v] + cx[1][u] * cy[1][v]
-                    T[9 * a + 3 * b + g] += acc
-    return [t % p for t in T]
 
 
 class _Prover:
@@ -138,7 +76,7 @@ class _Prover:
                 self.one_round(*v)
             else:
                 self.one_round(v[0], self.claim - v[0], v[1])
-        elif nb == 2:  # host.hpp two_rounds
+        elif nb == 2:  # gkr_rounds.hpp two_rounds
             e0 = v[0] + v[2]
             e1 = v[4] + v[8] if first else self.claim - e0
             r = self.one_round(e0, e1, v[5] + v[6])
@@ -147,7 +85,7 @@ class _Prover:
             f0 = (L0 * v[0] + L1 * v[4] + L2 * v[5]) % p
             f2 = (L0 * v[3] + L1 * v[7] + L2 * v[1]) % p
             self.one_round(f0, self.claim - f0, f2)
-        else:  # host.hpp three_rounds: X(t) Y(t) = (1-t)^2 m0 + t^2 m1 + t(1-t) ms
+        else:  # gkr_rounds.hpp three_rounds: X(t) Y(t) = (1-t)^2 m0 + t^2 m1 + t(1-t) ms
             T = v
             at2 = lambda m0, m1, ms: m0 + 4 * m1 - 2 * ms  # noqa: E731
             wts = lambda t: [(1 - t) * (1 - t) % p, t * t % p, t * (1 - t) % p]  # noqa: E731
@@ -257,7 +195,7 @@ def test_shipped_schedule_matches_single_process(tmp_path, world, n_local, gathe
 
 
 def test_schedule_shapes():
-    """The schedule helper against hand-derived schedules (host.hpp gkr_phase)."""
+    """The schedule helper against hand-derived schedules (gkr_plan.hpp plan_phase)."""
     import gkr_schedule as gs
 
     assert gs.bounds(24) == [3, 6, 9, 12, 14, 16, 18, 20, 22, 24]  # d0t, t33 x3, dm3, doubles

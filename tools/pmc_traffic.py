@@ -5,7 +5,7 @@ dispatch), takes the dispatches of the LAST proof in the run (from its
 k_gkr_round0), and reports per dispatch traffic = 2 * FETCH_SIZE + WRITE_SIZE
 bytes (the x2 is the gfx950 correction for wide coalesced streaming reads,
 MI355X_MICROARCH.md "HBM") beside the algorithmic bytes of the step schedule
-(host.hpp gkr_phase): round 0 256 B per pair, a single round 768 B per output
+(gkr_plan.hpp plan_phase, bytes in host.hpp): round 0 256 B per pair, a single round 768 B per output
 pair, a double step 1536 B (one pending challenge) or 2560 B (two) per quad,
 the persistent tail the sum of its double steps; k_gkr_d0m 128 B per input
 index, k_gkr_dm 2560 B per quad, k_gkr_d0t 128 B per input index, k_gkr_t33
@@ -32,7 +32,7 @@ def dispatches(path, counter):
 
 def schedule(n, dtail_max_quads=4096, d0=True, dm_min_quads=1 << 17, d0t=True):
     """(symbol prefix, algorithmic bytes) per dispatch of one proof (one GPU), as
-    host.hpp gkr_phase builds it. d0t (ZK_D0T, default, n >= 11): k_gkr_d0t
+    gkr_plan.hpp plan_phase builds it. d0t (ZK_D0T, default, n >= 11): k_gkr_d0t
     (rounds 0-2, 128 B per input index), nt k_gkr_t33 (9216 B per octant), one
     k_gkr_dm3 (4608 B per quad), then double steps with two pending challenges.
     Else d0 (ZK_D0): an even n starts with k_gkr_d0m (rounds 0 and 1). Double

@@ -130,22 +130,11 @@ void gkr_layer_two_phase(zk_ctx* c, const Fe* w, const Fe* wt, const uint8_t* op
 // summed unreduced and reduced once.
 template <class F>
 void host_layer_phase(std::vector<Fe> (&T)[4], uint32_t n, uint32_t k0, zk_transcript* tr, GkrOut& out) {
-  using namespace zk;
   Fe r;
   for (uint32_t i = 0; i < n; ++i) {
-    const size_t h = T[0].size() / 2;
-    uint64_t a0[9] = {0}, a1[9] = {0}, a2[9] = {0};
-    for (size_t j = 0; j < h; ++j) {
-      h64::V x2[4];
-      for (int t = 0; t < 4; ++t) x2[t] = h64::of(hfe_sub<F>(hfe_add<F>(T[t][j + h], T[t][j + h]), T[t][j]));
-      h64::mac_wide(a0, h64::of(T[0][j]), h64::of(T[1][j]));
-      h64::mac_wide(a0, h64::of(T[2][j]), h64::of(T[3][j]));
-      h64::mac_wide(a1, h64::of(T[0][j + h]), h64::of(T[1][j + h]));
-      h64::mac_wide(a1, h64::of(T[2][j + h]), h64::of(T[3][j + h]));
-      h64::mac_wide(a2, x2[0], x2[1]);
-      h64::mac_wide(a2, x2[2], x2[3]);
-    }
-    finish_round<F>(tr, wide_to_fe<F>(a0), wide_to_fe<F>(a1), wide_to_fe<F>(a2), k0 + i, out, r);
+    Fe e0, e1, e2;
+    host_round_sums<F, true>(T, e0, e2, &e1);
+    finish_round<F>(tr, e0, e1, e2, k0 + i, out, r);
     host_fold<F>(T, r);  // (after the last round: the tables at the phase's point, one entry each)
   }
 }

@@ -1,6 +1,6 @@
 // Host-side core shared by the library's translation units (zk_sumcheck.hip,
 // gkr_circuit.hip, kzg.hip, blob.hip): errors and the C-ABI guard, field
-// dispatch and representation conversion, the transcript, the device context
+// dispatch and representation conversion, the device context
 // (zk_ctx), kernel launch / timing, and the sum-check / GKR round drivers.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -23,7 +23,8 @@
 #include "keccak.hpp"
 #include "kernels.hpp"
 #include "mfma.hpp"
-#include "hfield.hpp"
+#include "gkr_plan.hpp"
+#include "gkr_rounds.hpp"
 
 using zk::Fe;
 
@@ -105,41 +106,7 @@ template <class F>
 zk_fe out_repr(zk_repr repr, const Fe& m) {  // Montgomery -> host scalar out
   return to_zk(repr == ZK_REPR_MONTGOMERY ? m : zk::fe_from_mont<F>(m));
 }
-template <class F>
-void canon_bytes(const Fe& m, uint8_t out[32]) {  // into_bigint().to_bytes_le()
-  const Fe c = zk::hfe_from_mont<F>(m);
-  memcpy(out, c.v, 32);
-}
 
-}  // namespace zkh
-using namespace zkh;
-
-// ===========================================================================
-// transcript (fiat_shamir_transcript.rs:5-37)
-// ===========================================================================
-struct zk_transcript {
-  zk::Keccak256 h;
-};
-
-namespace zkh {
-// get_random_challenge: d = finalize_reset(); append(d); from_le_bytes_mod_order(d)
-template <class F>
-Fe challenge(zk_transcript* t) {
-  uint8_t d[32];
-  t->h.finalize_reset(d);
-  t->h.update(d, 32);
-  Fe x;
-  memcpy(x.v, d, 32);
-  return zk::hfe_to_mont<F>(x);  // LE integer mod p (2^256 < 6p), Montgomery image
-}
-template <class F>
-void absorb(zk_transcript* t, const Fe* m, size_t n) {  // append(fq_vec_to_bytes(v))
-  uint8_t b[32];
-  for (size_t i = 0; i < n; ++i) {
-    canon_bytes<F>(m[i], b);
-    t->h.update(b, 32);
-  }
-}
 }  // namespace zkh
 using namespace zkh;
 
@@ -712,35 +679,11 @@ inline void ensure_partials(zk_ctx* c, uint32_t nv) {
 }
 
 // ---------------------------------------------------------------------------
-// GKR sum-check rounds
+// GKR sum-check rounds: the step schedule comes from gkr_plan.hpp
+// (plan_phase), a step's sums become rounds in gkr_rounds.hpp; here the steps
+// are enqueued and their sums collected.
 // ---------------------------------------------------------------------------
-struct GkrOut {
-  std::vector<Fe> coeffs;     // 3 per round (Montgomery), trimmed count in ncoeffs
-  std::vector<uint8_t> ncoeffs;
-  std::vector<Fe> challenges;
-};
-
-// Round polynomial through (0,e0),(1,e1),(2,e2) — the unique degree<=2
-// polynomial UnivariatePoly::interpolate returns (univariate_polynomial_dense.rs:48-74),
-// trailing zero coefficients trimmed (:14-18). Absorbs it, draws r_k and
-// returns s_k(r_k).
-template <class F>
-Fe finish_round(zk_transcript* tr, const Fe& e0, const Fe& e1, const Fe& e2, uint32_t k, GkrOut& out, Fe& r) {
-  using namespace zk;
-  Fe c[3];
-  c[0] = e0;
-  c[2] = hfe_half<F>(hfe_add<F>(hfe_sub<F>(e0, hfe_add<F>(e1, e1)), e2));
-  c[1] = hfe_sub<F>(hfe_sub<F>(e1, e0), c[2]);
-  int m = 3;
-  while (m > 0 && fe_is_zero<F>(c[m - 1])) --m;
-  absorb<F>(tr, c, (size_t)m);
-  out.ncoeffs[k] = (uint8_t)m;
-  for (int i = 0; i < 3; ++i) out.coeffs[3 * k + i] = i < m ? c[i] : fe_zero<F>();
-  r = challenge<F>(tr);
-  out.challenges[k] = r;
-  // UnivariatePoly::evaluate(r) (:20-26) via Horner — same field value
-  return hfe_add<F>(c[0], hfe_mul<F>(r, hfe_add<F>(c[1], hfe_mul<F>(r, c[2]))));
-}
+static_assert(zk::kD0TCats == 27 && zk::kD0Cats == 9 && zk::kDCats == 8, "gkr_rounds.hpp three_rounds / two_rounds");
 
 // Posts the challenge of a finished round to the pinned slot the next
 // pre-enqueued round kernel polls. If the host unwinds mid-proof (exception),
@@ -814,20 +757,6 @@ inline bool prelaunch(zk_ctx* c, uint32_t nv) {
   return c->prelaunch && nv > 1 && (c->comm != COMM_HOST || c->host_prelaunch);
 }
 
-// Run `nv` rounds over 4 device tables of 2^nv elements starting at global
-// round k0, as a sequence of steps:
-//   round 0        k_gkr_round0: e0, e1, e2 on the input tables;
-//   single round i k_gkr_round / k_gkr_round_lanes: fold by r_{i-1}, e0, e2;
-//   double (i,i+1) k_gkr_dround: apply the pending challenges, rounds i and
-//                  i+1 from one pass (default from round 2 on; an odd count
-//                  of remaining rounds puts one single round first);
-//   tail           (ZK_DROUND=0) k_gkr_tail: the small rounds in one kernel.
-// e1 of every round after the first is derived on the host as
-// s_{k-1}(r_{k-1}) - e0, exact because A*S + M*P has degree 2 per variable.
-// Pre-enqueued (default): every step (and, across ranks over RCCL, its
-// all-reduce + publish) is enqueued before round 0's sums are read; each
-// waits in-kernel for the challenges the host posts. On return `cur` holds
-// tables of 2^pend elements with the last `pend` challenges not yet applied.
 // Small rounds in one persistent kernel (k_gkr_tail, ZK_DROUND=0 only)?
 // Pre-enqueued only, and not when each round's sums take an RCCL all-reduce
 // on the stream (the kernel would hold the stream).
@@ -836,444 +765,252 @@ inline bool use_tail(zk_ctx* c, bool across_ranks) {
   return c->tail && !(across_ranks && multi_rank(c) && (c->comm == COMM_RCCL || c->peer));
 }
 constexpr size_t kTailRelayBytes = 64 * sizeof(zk::RPost);  // 64 relay slots (k_gkr_tail: RWait, k_gkr_dtail: RPost)
-inline size_t tail_bytes(uint64_t h0) { return kTailRelayBytes + 16 * h0 * sizeof(Fe); }
-
-struct GStep {
-  int kind;        // GS_*
-  uint32_t i;      // first round (local)
-  int np;          // double / dtail: pending challenges at entry (1 or 2)
-  uint32_t nd = 0; // dtail: double steps it runs
-  bool dfs = false;  // dtail: device-side Fiat-Shamir between its steps (ZK_DEVICE_FS)
-};
-enum {
-  GS_ROUND0 = 0, GS_SINGLE = 1, GS_DOUBLE = 2, GS_TAIL = 3, GS_DTAIL = 4, GS_D0 = 5, GS_D0T = 6, GS_T32 = 7, GS_T33 = 8,
-  GS_HOST = 11   // the last rounds on the host, from the tables the persistent tail's last step hands over
-};
-
-// Host rounds (ZK_HOST_ROUNDS, default 4; only where the caller does not
-// need the final tables, host_ok): a double step on a few-element table is
-// one wave's dependent chain of 256-bit multiplies (~7 us) plus a hand-off
-// (~5 us), while the host does the same round in about a microsecond. So
-// the persistent tail's last device step stores its output tables (4 x
-// 2^(H+2) elements, 8 KiB at H = 4) to pinned host memory, and the host folds
-// them by that step's two challenges and runs the last H rounds itself — the
-// reference's own arithmetic (gkr_prove's loop, sum_check_protocol.rs:86-115,
-// with get_round_partial_polynomial_proof_gkr :152-166 and partial_evaluate
-// multilinear_polynomial_evaluation.rs:52-63), same field values.
-template <class F>
-void host_fold(std::vector<Fe> (&T)[4], const Fe& r) {
-  for (auto& t : T) {
-    const size_t h = t.size() / 2;
-    for (size_t j = 0; j < h; ++j) t[j] = zk::hfe_add<F>(t[j], zk::hfe_mul<F>(r, zk::hfe_sub<F>(t[j + h], t[j])));
-    t.resize(h);
-  }
-}
-// e0 = sum [A S + M P](lo), e2 = sum [A S + M P](2 hi - lo) over the pairs of the current tables
-// (products summed unreduced, one reduction per value)
-template <class F>
-void host_round_sums(const std::vector<Fe> (&T)[4], Fe& e0, Fe& e2) {
-  using namespace zk;
-  const size_t h = T[0].size() / 2;
-  uint64_t a0[9] = {0}, a2[9] = {0};
-  for (size_t j = 0; j < h; ++j) {
-    h64::V x2[4];
-    for (int t = 0; t < 4; ++t) x2[t] = h64::of(hfe_sub<F>(hfe_add<F>(T[t][j + h], T[t][j + h]), T[t][j]));
-    h64::mac_wide(a0, h64::of(T[0][j]), h64::of(T[1][j]));
-    h64::mac_wide(a0, h64::of(T[2][j]), h64::of(T[3][j]));
-    h64::mac_wide(a2, x2[0], x2[1]);
-    h64::mac_wide(a2, x2[2], x2[3]);
-  }
-  e0 = wide_to_fe<F>(a0);
-  e2 = wide_to_fe<F>(a2);
+// What the schedule of a phase over 2^nv elements reads from the context.
+inline PlanKnobs plan_knobs(zk_ctx* c, uint32_t nv, bool across_ranks) {
+  PlanKnobs k;
+  k.pre = prelaunch(c, nv);
+  k.dround = c->dround;
+  k.d0 = c->d0 > 0;
+  k.d0t = c->d0t;
+  k.dtail = c->dtail;
+  k.use_tail = use_tail(c, across_ranks);
+  k.cross_ranks = across_ranks && multi_rank(c);
+  k.device_fs = c->device_fs;
+  k.dtail_max_quads = c->dtail_max_quads;
+  k.tail_max_pairs = c->tail_max_pairs;
+  k.host_rounds = c->host_rounds;
+  k.num_cus = (uint32_t)c->num_cus;
+  k.t33_oct64_min = c->t33_oct64_min;
+  k.mall_order = c->mall_order;
+  return k;
 }
 
-// The four tables folded by every challenge of a phase (the multilinear
-// extensions at the phase's point), when its last rounds ran on the host.
-struct FinalVals {
-  Fe v[4];
-  bool ok = false;
-};
-
-// gather_max > 0 (sharded phases): stop after the first step boundary b with
-// nv - b <= gather_max; *stop = b (nv when the phase runs to its end).
-// fin: filled (fin->ok) when the phase ends in host rounds — one more host
-// fold of the last two entries by the last challenge.
-template <class F>
-void gkr_phase(zk_ctx* c, const Fe* cur[4], uint32_t nv, uint32_t k0, bool across_ranks, zk_transcript* tr,
-               GkrOut& out, Fe& claim, Fe& r, uint32_t& pend, bool host_ok = false, uint32_t gather_max = 0,
-               uint32_t* stop = nullptr, FinalVals* fin = nullptr) {
-  if (fin) fin->ok = false;
-  const uint64_t L = (uint64_t)1 << nv;
-  const bool pre = prelaunch(c, nv);
-  std::vector<GStep> steps;
-  // rounds 0 and 1 in one pass over the inputs (default; same-box A/B at n = 24:
-  // BN254 Fr 1.72-1.74 vs 1.82-1.85 ms, BLS12-381 Fr 1.76 vs 1.83 ms)
-  // Three rounds per pass (ZK_D0T, nv >= 11): rounds 0-2 over the inputs
-  // (k_gkr_d0t), then nt triple steps that fold by the three pending
-  // challenges and run three rounds (k_gkr_t33), one two-round step that
-  // folds by three (k_gkr_dm3), and double steps (the small ones in the
-  // persistent k_gkr_dtail). nt: the largest count leaving an even number
-  // R >= 12 of rounds after the triples, else the smallest leaving an even
-  // R >= 8 (every matrix-core step needs >= 64 quads / 32 octants).
-  // (Measured and removed: triple steps to the end in a persistent MFMA
-  // kernel, and rounds 0-3 in the input pass with a fold by four)
-  const bool d0t = c->dround && c->d0t && nv >= 11;
-  int nt = -1;
-  if (d0t)
-    for (int k = 0; 3 + 3 * k + 8 <= (int)nv; ++k) {
-      const int R = (int)nv - 3 - 3 * k;
-      if (R % 2 == 0 && (R >= 12 || nt < 0)) nt = k;
-    }
-  const bool d0t_doubles = d0t && nt >= 0;
-  const bool d0 = !d0t_doubles && c->dround && c->d0 > 0 && nv >= 2 && nv % 2 == 0;
-  if (nv >= 1) steps.push_back({d0t_doubles ? GS_D0T : (d0 ? GS_D0 : GS_ROUND0), 0, 0});
-  if (d0t_doubles) {
-    for (int k = 0; k < nt; ++k) steps.push_back({GS_T33, 3u + 3u * k, 3});
-    steps.push_back({GS_T32, 3u + 3u * nt, 3});
+// The buffers a plan implies, before anything of the phase is enqueued.
+inline void prepare_phase_buffers(zk_ctx* c, const PhasePlan& pl) {
+  if (pl.fslog && !c->h_fslog) {
+    HIPCK(hipHostMalloc(reinterpret_cast<void**>(&c->h_fslog), 64 * sizeof(zk::FsLog),
+                        hipHostMallocMapped | hipHostMallocCoherent));
+    memset(c->h_fslog, 0, 64 * sizeof(zk::FsLog));
   }
-  if (c->dround) {
-    uint32_t i = d0t_doubles ? 5u + 3u * nt : (d0 ? 2 : 1);
-    int np = d0t_doubles || d0 ? 2 : 1;  // challenges pending at the first double step
-    if (!d0 && !d0t_doubles) {
-      if (nv >= 2) steps.push_back({GS_SINGLE, i++, 0});
-      if (nv >= 3 && (nv - 2) % 2 == 1) steps.push_back({GS_SINGLE, i++, 0});
-    }
-    for (; i + 1 < nv; i += 2, np = 2) steps.push_back({GS_DOUBLE, i, np});
-    // host rounds: the last H rounds, if they are whole double steps and the
-    // persistent tail keeps >= 2 device steps before them
-    // (H = ZK_HOST_ROUNDS, or fewer when that leaves the tail < 2 steps: odd
-    // round counts at n = 9, 11 take H = 2)
-    uint32_t hostH = 0;
-    if (host_ok && pre && c->dtail && use_tail(c, across_ranks) && !(across_ranks && multi_rank(c)) && c->host_rounds >= 2) {
-      for (uint32_t H = c->host_rounds & ~1u; H >= 2 && hostH == 0; H -= 2) {
-        size_t k = steps.size();
-        uint32_t got = 0;
-        while (got < H && k > 0 && steps[k - 1].kind == GS_DOUBLE && steps[k - 1].np == 2) {
-          --k;
-          got += 2;
-        }
-        size_t smalls = 0;  // device double steps left for the persistent tail
-        for (size_t q = 0; q < k; ++q)
-          if (steps[q].kind == GS_DOUBLE && (L >> steps[q].i) / 4 <= c->dtail_max_quads) ++smalls;
-        if (got == H && smalls >= 2 && k == steps.size() - H / 2) {
-          steps.resize(k);
-          hostH = H;
-        }
-      }
-    }
-    // the small doubles (>= 2 of them) in one persistent kernel
-    if (pre && c->dtail && use_tail(c, across_ranks)) {
-      size_t d0 = 0;
-      while (d0 < steps.size() && !(steps[d0].kind == GS_DOUBLE && (L >> steps[d0].i) / 4 <= c->dtail_max_quads)) ++d0;
-      const size_t nd = steps.size() - d0;
-      if (d0 < steps.size() && nd >= 2 && nd <= 64) {
-        const GStep first = steps[d0];
-        steps.resize(d0);
-        // device-side Fiat-Shamir between the tail's steps: one rank's sums only
-        // (a sharded tail's sums are all-reduced on the host between steps)
-        const bool dfs = c->device_fs && !(across_ranks && multi_rank(c));
-        steps.push_back({GS_DTAIL, first.i, first.np, (uint32_t)nd, dfs});
-        if (dfs && !c->h_fslog) {
-          HIPCK(hipHostMalloc(reinterpret_cast<void**>(&c->h_fslog), 64 * sizeof(zk::FsLog),
-                              hipHostMallocMapped | hipHostMallocCoherent));
-          memset(c->h_fslog, 0, 64 * sizeof(zk::FsLog));
-        }
-        const uint64_t Q0 = (L >> first.i) / 4;
-        const size_t had = c->tailbuf.bytes;
-        c->tailbuf.ensure(kTailRelayBytes + zk::dtail_region(Q0, (uint32_t)nd) * sizeof(Fe));
-        if (c->tailbuf.bytes != had) HIPCK(hipMemset(c->tailbuf.p, 0, kTailRelayBytes));  // relay tags at rest
-      }
-    }
-    if (hostH > 0) {
-      if (steps.empty() || steps.back().kind != GS_DTAIL) fail(ZK_EINVAL, "internal: host rounds need the persistent tail");
-      const size_t need = (size_t)4 * ((size_t)1 << (hostH + 2)) * sizeof(Fe);
-      if (c->h_tab_bytes < need) {
-        if (c->h_tab) HIPCK(hipHostFree(c->h_tab));
-        c->h_tab = nullptr;
-        c->h_tab_bytes = 0;
-        HIPCK(hipHostMalloc(reinterpret_cast<void**>(&c->h_tab), need, hipHostMallocMapped | hipHostMallocCoherent));
-        c->h_tab_bytes = need;
-      }
-      steps.push_back({GS_HOST, nv - hostH, 2});
-    }
+  if (pl.tail_elems > 0) {
+    const size_t had = c->tailbuf.bytes;
+    c->tailbuf.ensure(kTailRelayBytes + pl.tail_elems * sizeof(Fe));
+    if (c->tailbuf.bytes != had) HIPCK(hipMemset(c->tailbuf.p, 0, kTailRelayBytes));  // relay tags at rest
+  }
+  if (c->h_tab_bytes < pl.host_tab_bytes) {
+    if (c->h_tab) HIPCK(hipHostFree(c->h_tab));
+    c->h_tab = nullptr;
+    c->h_tab_bytes = 0;
+    HIPCK(hipHostMalloc(reinterpret_cast<void**>(&c->h_tab), pl.host_tab_bytes, hipHostMallocMapped | hipHostMallocCoherent));
+    c->h_tab_bytes = pl.host_tab_bytes;
+  }
+}
+
+// How a step gets its challenge(s): pre-enqueued, it waits in-kernel for the
+// tag (returned in rtag) the host posts them under; launched after them, it
+// carries the values.
+inline zk::DIn make_din(zk_ctx* c, bool pre, uint32_t& rtag, const Fe& ra, const Fe& rb, const Fe& rab) {
+  zk::DIn d{};
+  if (pre) {
+    d.host = h_rpost(c);
+    d.relay = d_rpost(c);
+    d.err = h_err(c);
+    d.tag = rtag = ++c->rtag;
   } else {
-    // first round >= 1 with <= tail_max_pairs pairs, if at least two rounds remain
-    uint32_t tail0 = nv;
-    if (pre && use_tail(c, across_ranks)) {
-      uint32_t i = 1;
-      while (i < nv && (L >> i) / 2 > c->tail_max_pairs) ++i;
-      if (i + 2 <= nv && nv - i <= 64) {
-        tail0 = i;
-        const size_t had = c->tailbuf.bytes;
-        c->tailbuf.ensure(tail_bytes((L >> i) / 2));  // before anything of this phase is enqueued
-        if (c->tailbuf.bytes != had) HIPCK(hipMemset(c->tailbuf.p, 0, kTailRelayBytes));  // relay tags at rest
-      }
-    }
-    for (uint32_t i = 1; i < nv; ++i) {
-      if (i == tail0) {
-        steps.push_back({GS_TAIL, i, 0});
-        break;
-      }
-      steps.push_back({GS_SINGLE, i, 0});
-    }
+    d.ra = ra;
+    d.rb = rb;
+    d.rab = rab;
   }
-  auto rounds_of = [&](const GStep& st) -> uint32_t {
-    switch (st.kind) {
-      case GS_DOUBLE: case GS_D0: case GS_T32: return 2;
-      case GS_D0T: case GS_T33: return 3;
-      case GS_DTAIL: return 2 * st.nd;
-      case GS_TAIL: case GS_HOST: return nv - st.i;
-      default: return 1;
-    }
-  };
-  uint32_t end = nv;  // rounds this phase runs
-  if (gather_max > 0) {  // sharded: stop at the first boundary leaving <= gather_max rounds (host.hpp gkr_prove_device)
-    for (size_t s = 0; s < steps.size(); ++s) {
-      const uint32_t b = steps[s].i + rounds_of(steps[s]);
-      const int k = steps[s].kind;
-      if (k == GS_TAIL || k == GS_DTAIL || k == GS_HOST) break;  // (persistent steps are not cut)
-      if (b < nv && nv - b <= gather_max) {
-        steps.resize(s + 1);
-        end = b;
-        break;
-      }
-    }
+  return d;
+}
+inline zk::RoundIn make_rin(zk_ctx* c, bool pre, uint32_t& rtag, const Fe& r) {
+  zk::RoundIn in{};
+  if (pre) {
+    in.host = h_rin(c);
+    in.relay = d_relay(c);
+    in.err = h_err(c);
+    in.tag = rtag = ++c->rtag;
+  } else {
+    in.r = r;
   }
-  if (stop) *stop = end;
-  const size_t ns = steps.size();
-  {  // the schedule covers rounds 0 .. end-1 exactly once, in order (checked before anything launches)
-    uint32_t next = 0;
-    for (const GStep& st : steps) {
-      if (st.i != next) fail(ZK_EINVAL, "internal: step schedule out of order");
-      next += rounds_of(st);
-    }
-    if (next != end) fail(ZK_EINVAL, "internal: step schedule does not cover every round");
-  }
-  // ZK_MALL_ORDER: the input pass groups its chunks by the first 64-octant
-  // k_gkr_t33's (16 of its 32-octant chunks per t33 chunk), that t33 takes them
-  // in reverse (mfma.hpp k_gkr_d0t / k_gkr_t33 `order`); needs both steps at
-  // these positions and the input pass's chunk count a multiple of 16
-  const bool oct64_3 = (L >> 6) / 64 >= (uint64_t)c->num_cus * c->t33_oct64_min;   // first t33: 64-octant
-  const bool oct64_6 = (L >> 9) / 64 >= (uint64_t)c->num_cus * c->t33_oct64_min;   // second t33: 64-octant
-  uint32_t d0t_order = c->mall_order && ns >= 2 && steps[0].kind == GS_D0T && steps[1].kind == GS_T33 &&
-                               ((L >> 3) / 32) % 16 == 0 && oct64_3 ? 1u : 0u;
-  if (d0t_order && c->mall_order >= 2 && ns >= 3 && steps[2].kind == GS_T33 && oct64_6 && ((L >> 6) / 64) % 8 == 0)
-    d0t_order = 2;
-  std::vector<zk::RoundSink> sinks(nv);  // per round (a double uses its first round's, a tail one per round)
-  std::vector<uint32_t> rtags(ns, 0);    // per step: the (first) challenge tag it waits for
-  int inbuf = -1;                        // work buffer holding cur (-1: the input tables)
-  Fe rz = zk::fe_zero<F>(), ra = rz, rb = rz;  // last three challenges (oldest first)
-  auto out_tables = [&](uint64_t size, Fe* nx[4]) {
+  return in;
+}
+
+// One phase in flight: `nv` rounds over 4 device tables of 2^nv elements
+// starting at global round k0, as the plan's steps:
+//   round 0        k_gkr_round0: e0, e1, e2 on the input tables;
+//   single round i k_gkr_round / k_gkr_round_lanes: fold by r_{i-1}, e0, e2;
+//   double (i,i+1) k_gkr_dround: apply the pending challenges, rounds i and
+//                  i+1 from one pass (default from round 2 on; an odd count
+//                  of remaining rounds puts one single round first);
+//   tail           (ZK_DROUND=0) k_gkr_tail: the small rounds in one kernel.
+// Pre-enqueued (default): every step (and, across ranks over RCCL, its
+// all-reduce + publish) is enqueued before round 0's sums are read; each
+// waits in-kernel for the challenges the host posts.
+template <class F>
+struct PhaseRun {
+  zk_ctx* c;
+  const Fe** cur;  // the current tables
+  uint32_t nv;
+  bool across_ranks, pre;
+  const PhasePlan& pl;
+  FinalVals* fin;
+  RoundState rs;
+  std::vector<zk::RoundSink> sinks;  // per round (a double uses its first round's, a tail one per round)
+  std::vector<uint32_t> rtags;       // per step: the (first) challenge tag it waits for
+  int inbuf;                         // work buffer holding cur (-1: the input tables)
+  PostR post;
+
+  void out_tables(uint64_t size, Fe* nx[4]) {
     const int ob = inbuf == 0 ? 1 : 0;
     Fe* w = c->work[ob].fe();
     for (int t = 0; t < 4; ++t) nx[t] = w + (uint64_t)t * size;
     inbuf = ob;
-  };
-  auto enqueue = [&](size_t si) {
-    const GStep& st = steps[si];
-    if (st.kind == GS_HOST) return;  // no kernel: the host runs these rounds
-    const uint32_t i = st.i;
-    const uint64_t size = L >> i;  // table length in round i
-    const uint64_t h = size / 2;   // pairs
-    sinks[i] = make_sink(c, across_ranks);
-    if (c->block_trace && (int)si == c->block_trace_step) sinks[i].btrace = c->block_trace;
-    const zk::RoundSink& sk = sinks[i];
+  }
+  // a step that wrote nx: the tables move on, its sums go to the ranks' reduction
+  void wrote(Fe* const nx[4], const zk::RoundSink& sk, int limbs) {
+    for (int t = 0; t < 4; ++t) cur[t] = nx[t];
+    enqueue_reduce(c, sk, across_ranks, limbs);
+  }
+
+  void enqueue_input(const GStep& st) {  // over the input tables, nothing written
+    const uint64_t size = (uint64_t)1 << nv, h = size / 2;
+    const zk::RoundSink& sk = sinks[0];
     if (st.kind == GS_ROUND0) {
       const uint32_t grid = grid_for(c, 2 * h, zk::k_gkr_round0<F>);
       launch(c, ZK_K_GKR_ROUND0, 256.0 * h, 6.0 * h, zk::k_gkr_round0<F>, grid, cur[0], cur[1], cur[2], cur[3], h, sk);
       enqueue_reduce(c, sk, across_ranks, 3 * 17);
-      return;
-    }
-    if (st.kind == GS_D0) {  // rounds 0 and 1 over the input tables (size 4Q), nothing written
-      const uint64_t Q = size / 4;
-      // products on the matrix cores (k_gkr_d0m, mfma.hpp)
-      const uint64_t nch = (Q + 31) / 32;
+    } else if (st.kind == GS_D0) {  // rounds 0 and 1 (size 4Q): products on the matrix cores (k_gkr_d0m, mfma.hpp)
+      const uint64_t Q = size / 4, nch = (Q + 31) / 32;
       const uint32_t res = grid_for(c, nch * zk::kBlock, zk::k_gkr_d0m<F>);
       const uint32_t grid = step_grid(c, res, (nch + 2 * zk::kD0MChunksMax - 1) / (2 * zk::kD0MChunksMax));
       launch(c, ZK_K_GKR_D0, 128.0 * size, 4.5 * size, zk::k_gkr_d0m<F>, grid, cur[0], cur[1], cur[2], cur[3], Q, sk);
       enqueue_reduce(c, sk, across_ranks, zk::kD0Limbs);
-      return;
-    }
-    if (st.kind == GS_D0T) {  // rounds 0, 1, 2 over the input tables (size 8 O), nothing written
+    } else {  // GS_D0T: rounds 0, 1, 2 (size 8 O)
       const uint64_t O = size / 8, nch = O / 32;
-      const uint32_t res = ((c->lc_loads & 1u) ? grid_for(c, 2 * nch * zk::kBlock, zk::k_gkr_d0t<F, true>)
-                                                : grid_for(c, 2 * nch * zk::kBlock, zk::k_gkr_d0t<F>)) & ~1u;
+      const auto kern = (c->lc_loads & 1u) ? zk::k_gkr_d0t<F, true> : zk::k_gkr_d0t<F>;
+      const uint32_t res = grid_for(c, 2 * nch * zk::kBlock, kern) & ~1u;
       const uint32_t grid = step_grid(c, res, std::max<uint64_t>(2, 2 * ((nch + zk::kD0TChunksMax - 1) / zk::kD0TChunksMax))) & ~1u;
-      const uint32_t order = d0t_order;
-      if (c->lc_loads & 1u)
-        launch(c, ZK_K_GKR_D0, 128.0 * size, 8.0 * size, zk::k_gkr_d0t<F, true>, grid, cur[0], cur[1], cur[2], cur[3], O, order, sk);
-      else
-        launch(c, ZK_K_GKR_D0, 128.0 * size, 8.0 * size, zk::k_gkr_d0t<F>, grid, cur[0], cur[1], cur[2], cur[3], O, order, sk);
+      launch(c, ZK_K_GKR_D0, 128.0 * size, 8.0 * size, kern, grid, cur[0], cur[1], cur[2], cur[3], O, pl.d0t_order, sk);
       enqueue_reduce(c, sk, across_ranks, zk::kD0TLimbs);
-      return;
     }
-    if (st.kind == GS_T32 || st.kind == GS_T33) {  // fold level i-3 by three challenges to level i
-      const uint64_t Q = size / 4;
-      Fe* nx[4];
-      out_tables(size, nx);
-      zk::DIn din{};
-      if (pre) {
-        din.host = h_rpost(c);
-        din.relay = d_rpost(c);
-        din.err = h_err(c);
-        din.tag = rtags[si] = ++c->rtag;
-      } else {
-        din.ra = rz;
-        din.rb = ra;
-        din.rab = rb;  // carries r_{i-1} for this step
-      }
-      if (st.kind == GS_T33) {  // rounds i .. i+2 over level i's octants: 27 moment sums
-        const uint64_t O = size / 8;
-        // 64-octant chunks while they still give every CU a chunk, else 32 (twice the blocks)
-        if (O / 64 >= (uint64_t)c->num_cus * c->t33_oct64_min) {
-          const uint64_t nch = O / 64;
-          const uint32_t res = grid_for(c, nch * zk::kBlock, zk::k_gkr_t33<F, 64>);
-          const uint32_t grid = step_grid(c, res, (nch + zk::kT33ChunksMax<64> - 1) / zk::kT33ChunksMax<64>);
-          const uint32_t order = si == 1 ? d0t_order : 0u;  // (the pass right after an ordered k_gkr_d0t)
-          const bool lc = c->t33_pipe && (c->lc_loads & (si == 1 ? 2u : 4u));
-          if (lc)
-            launch(c, ZK_K_GKR_T33, 9216.0 * O, 96.0 * O, zk::k_gkr_t33<F, 64, true, true>, grid, cur[0], cur[1], cur[2],
-                   cur[3], nx[0], nx[1], nx[2], nx[3], O, order, din, sk);
-          else if (c->t33_pipe)
-            launch(c, ZK_K_GKR_T33, 9216.0 * O, 96.0 * O, zk::k_gkr_t33<F, 64, true>, grid, cur[0], cur[1], cur[2],
-                   cur[3], nx[0], nx[1], nx[2], nx[3], O, order, din, sk);
-          else
-            launch(c, ZK_K_GKR_T33, 9216.0 * O, 96.0 * O, zk::k_gkr_t33<F, 64>, grid, cur[0], cur[1], cur[2], cur[3],
-                   nx[0], nx[1], nx[2], nx[3], O, order, din, sk);
-        } else {
-          const uint64_t nch = O / 32;
-          const uint32_t res = grid_for(c, nch * zk::kBlock, zk::k_gkr_t33<F, 32>);
-          const uint32_t grid = step_grid(c, res, (nch + zk::kT33ChunksMax<32> - 1) / zk::kT33ChunksMax<32>);
-          launch(c, ZK_K_GKR_T33, 9216.0 * O, 96.0 * O, zk::k_gkr_t33<F, 32>, grid, cur[0], cur[1], cur[2], cur[3],
-                 nx[0], nx[1], nx[2], nx[3], O, 0u, din, sk);
-        }
-        for (int t = 0; t < 4; ++t) cur[t] = nx[t];
-        enqueue_reduce(c, sk, across_ranks, zk::kD0TLimbs);
-        return;
-      }
-      const uint64_t nch = Q / zk::kDMQuads;
+  }
+  void enqueue_by_three(size_t si) {  // GS_T32 / GS_T33: fold level i-3 by three challenges to level i
+    const GStep& st = pl.steps[si];
+    const uint64_t size = ((uint64_t)1 << nv) >> st.i;
+    const zk::RoundSink& sk = sinks[st.i];
+    Fe* nx[4];
+    out_tables(size, nx);
+    const zk::DIn din = make_din(c, pre, rtags[si], rs.rz, rs.ra, rs.rb);  // (rab carries r_{i-1} for this step)
+    if (st.kind == GS_T32) {
+      const uint64_t Q = size / 4, nch = Q / zk::kDMQuads;
       const uint32_t res = grid_for(c, nch * zk::kBlock, zk::k_gkr_dm3<F>);
       const uint32_t grid = step_grid(c, res, (nch + zk::kDMChunksMax - 1) / zk::kDMChunksMax);
       launch(c, ZK_K_GKR_DM, 4608.0 * Q, 48.0 * Q, zk::k_gkr_dm3<F>, grid, cur[0], cur[1], cur[2], cur[3], nx[0],
              nx[1], nx[2], nx[3], Q, din, sk);
-      for (int t = 0; t < 4; ++t) cur[t] = nx[t];
-      enqueue_reduce(c, sk, across_ranks, zk::kDLimbs);
-      return;
+      return wrote(nx, sk, zk::kDLimbs);
     }
-    if (st.kind == GS_TAIL) {
-      // rounds i .. nv-1: consecutive sink and challenge tags, fresh table
-      // regions in tailbuf (round m: 4 tables of 2 (h >> m) elements)
-      const uint32_t nr = nv - i;
-      for (uint32_t m = 1; m < nr; ++m) sinks[i + m] = make_sink(c, across_ranks);
-      zk::TailArgs a{};
-      for (int t = 0; t < 4; ++t) a.in[t] = cur[t];
-      a.relay = reinterpret_cast<zk::RWait*>(c->tailbuf.p);
-      a.out = reinterpret_cast<Fe*>(reinterpret_cast<char*>(c->tailbuf.p) + kTailRelayBytes);
-      a.h0 = h;
-      a.nrounds = nr;
-      a.host = h_rin(c);
-      a.err = h_err(c);
-      rtags[si] = c->rtag + 1;
-      c->rtag += nr;
-      a.rtag0 = rtags[si];
-      if (c->tail_trace) a.trace = reinterpret_cast<uint64_t*>(c->tail_trace);
-      const uint64_t want = (8 * h + zk::kBlock - 1) / zk::kBlock;
-      const uint32_t grid = (uint32_t)std::min<uint64_t>(want, (uint64_t)c->num_cus);  // one block per CU: co-resident
-      const double pairs = (double)(2 * h - (h >> (nr - 1)));
-      launch(c, ZK_K_GKR_TAIL, 768.0 * pairs, 12.0 * pairs, zk::k_gkr_tail<F>, grid, a, sk);
-      const uint64_t hl = h >> (nr - 1);  // pairs of the last round
-      Fe* last = a.out + zk::tail_region(h, nr - 1);
-      for (int t = 0; t < 4; ++t) cur[t] = last + (uint64_t)t * 2 * hl;
-      return;
+    // rounds i .. i+2 over level i's octants: 27 moment sums; 64-octant chunks
+    // while they still give every CU a chunk, else 32 (twice the blocks)
+    const uint64_t O = size / 8;
+    const bool o64 = O / 64 >= (uint64_t)c->num_cus * c->t33_oct64_min;
+    const bool lc = c->t33_pipe && (c->lc_loads & (si == 1 ? 2u : 4u));
+    const auto kern = !o64 ? zk::k_gkr_t33<F, 32>
+                           : (lc ? zk::k_gkr_t33<F, 64, true, true> : (c->t33_pipe ? zk::k_gkr_t33<F, 64, true> : zk::k_gkr_t33<F, 64>));
+    const uint64_t nch = O / (o64 ? 64 : 32), chmax = o64 ? zk::kT33ChunksMax<64> : zk::kT33ChunksMax<32>;
+    const uint32_t grid = step_grid(c, grid_for(c, nch * zk::kBlock, kern), (nch + chmax - 1) / chmax);
+    const uint32_t order = o64 && si == 1 ? pl.d0t_order : 0u;  // (the pass right after an ordered k_gkr_d0t)
+    launch(c, ZK_K_GKR_T33, 9216.0 * O, 96.0 * O, kern, grid, cur[0], cur[1], cur[2], cur[3], nx[0], nx[1], nx[2], nx[3], O,
+           order, din, sk);
+    wrote(nx, sk, zk::kD0TLimbs);
+  }
+  void enqueue_tail(size_t si) {
+    // rounds i .. nv-1: consecutive sink and challenge tags, fresh table
+    // regions in tailbuf (round m: 4 tables of 2 (h >> m) elements)
+    const uint32_t i = pl.steps[si].i, nr = nv - i;
+    const uint64_t h = (((uint64_t)1 << nv) >> i) / 2;
+    for (uint32_t m = 1; m < nr; ++m) sinks[i + m] = make_sink(c, across_ranks);
+    zk::TailArgs a{};
+    for (int t = 0; t < 4; ++t) a.in[t] = cur[t];
+    a.relay = reinterpret_cast<zk::RWait*>(c->tailbuf.p);
+    a.out = reinterpret_cast<Fe*>(reinterpret_cast<char*>(c->tailbuf.p) + kTailRelayBytes);
+    a.h0 = h;
+    a.nrounds = nr;
+    a.host = h_rin(c);
+    a.err = h_err(c);
+    a.rtag0 = rtags[si] = c->rtag + 1;
+    c->rtag += nr;
+    if (c->tail_trace) a.trace = reinterpret_cast<uint64_t*>(c->tail_trace);
+    const uint64_t want = (8 * h + zk::kBlock - 1) / zk::kBlock;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(want, (uint64_t)c->num_cus);  // one block per CU: co-resident
+    const double pairs = (double)(2 * h - (h >> (nr - 1)));
+    launch(c, ZK_K_GKR_TAIL, 768.0 * pairs, 12.0 * pairs, zk::k_gkr_tail<F>, grid, a, sinks[i]);
+    const uint64_t hl = h >> (nr - 1);  // pairs of the last round
+    Fe* last = a.out + zk::tail_region(h, nr - 1);
+    for (int t = 0; t < 4; ++t) cur[t] = last + (uint64_t)t * 2 * hl;
+  }
+  void enqueue_dtail(size_t si) {
+    const GStep& st = pl.steps[si];
+    const uint64_t Q0 = (((uint64_t)1 << nv) >> st.i) / 4;
+    for (uint32_t d = 1; d < st.nd; ++d) sinks[st.i + 2 * d] = make_sink(c, across_ranks);
+    zk::DTailArgs a{};
+    for (int t = 0; t < 4; ++t) a.in[t] = cur[t];
+    a.relay = reinterpret_cast<zk::RPost*>(c->tailbuf.p);
+    a.out = reinterpret_cast<Fe*>(reinterpret_cast<char*>(c->tailbuf.p) + kTailRelayBytes);
+    a.Q0 = Q0;
+    a.nsteps = st.nd;
+    a.np0 = (uint32_t)st.np;
+    a.host = h_rpost(c);
+    a.err = h_err(c);
+    a.rtag0 = rtags[si] = c->rtag + 1;
+    c->rtag += st.nd;
+    if (c->tail_trace) a.trace = c->tail_trace;
+    if (si + 1 < pl.steps.size() && pl.steps[si + 1].kind == GS_HOST) a.host_tab = c->h_tab;
+    a.fslog = c->h_fslog;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(
+        {(Q0 + zk::kDQuads - 1) / zk::kDQuads, (uint64_t)std::min<uint32_t>(c->dtail_blocks, 64u), (uint64_t)c->num_cus});
+    double bytes = 0, muls = 0;
+    for (uint32_t d = 0; d < st.nd; ++d) {
+      const bool two = d > 0 || st.np == 2;
+      bytes += (two ? 2560.0 : 1536.0) * (Q0 >> (2 * d));
+      muls += (two ? 40.0 : 24.0) * (Q0 >> (2 * d));
     }
-    if (st.kind == GS_DTAIL) {
-      const uint64_t Q0 = size / 4;
-      for (uint32_t d = 1; d < st.nd; ++d) sinks[i + 2 * d] = make_sink(c, across_ranks);
-      zk::DTailArgs a{};
-      for (int t = 0; t < 4; ++t) a.in[t] = cur[t];
-      a.relay = reinterpret_cast<zk::RPost*>(c->tailbuf.p);
-      a.out = reinterpret_cast<Fe*>(reinterpret_cast<char*>(c->tailbuf.p) + kTailRelayBytes);
-      a.Q0 = Q0;
-      a.nsteps = st.nd;
-      a.np0 = (uint32_t)st.np;
-      a.host = h_rpost(c);
-      a.err = h_err(c);
-      rtags[si] = c->rtag + 1;
-      c->rtag += st.nd;
-      a.rtag0 = rtags[si];
-      if (c->tail_trace) a.trace = c->tail_trace;
-      if (si + 1 < ns && steps[si + 1].kind == GS_HOST) a.host_tab = c->h_tab;
-      a.fslog = c->h_fslog;
-      const uint32_t grid = (uint32_t)std::min<uint64_t>(
-          {(Q0 + zk::kDQuads - 1) / zk::kDQuads, (uint64_t)std::min<uint32_t>(c->dtail_blocks, 64u), (uint64_t)c->num_cus});
-      double bytes = 0, muls = 0;
-      for (uint32_t d = 0; d < st.nd; ++d) {
-        const bool two = d > 0 || st.np == 2;
-        bytes += (two ? 2560.0 : 1536.0) * (Q0 >> (2 * d));
-        muls += (two ? 40.0 : 24.0) * (Q0 >> (2 * d));
-      }
-      if (st.dfs)
-        launch(c, ZK_K_GKR_DTAIL, bytes, muls, zk::k_gkr_dtail<F, true>, std::max<uint32_t>(grid, 1u), a, sk);
-      else
-        launch(c, ZK_K_GKR_DTAIL, bytes, muls, zk::k_gkr_dtail<F, false>, std::max<uint32_t>(grid, 1u), a, sk);
-      const uint64_t Ql = Q0 >> (2 * (st.nd - 1));
-      Fe* last = a.out + zk::dtail_region(Q0, st.nd - 1);
-      for (int t = 0; t < 4; ++t) cur[t] = last + (uint64_t)t * 4 * Ql;
-      return;
-    }
-    if (st.kind == GS_DOUBLE) {
-      // input: level i - np (size << np), output Z: level i (size = 4Q)
-      const uint64_t Q = size / 4;
-      Fe* nx[4];
-      out_tables(size, nx);
-      zk::DIn din{};
-      if (pre) {
-        din.host = h_rpost(c);
-        din.relay = d_rpost(c);
-        din.err = h_err(c);
-        din.tag = rtags[si] = ++c->rtag;
-      } else if (st.np == 2) {
-        din.ra = ra;
-        din.rb = rb;
-        din.rab = zk::fe_mul<F>(ra, rb);
-      } else {
-        din.rb = rb;
-      }
-      const double bytes = (st.np == 2 ? 2560.0 : 1536.0) * Q, muls = (st.np == 2 ? 40.0 : 24.0) * Q;
-      if (st.np == 2 && c->dm && Q >= std::max<uint64_t>(c->dm_min_quads, zk::kDMQuads)) {  // matrix cores (mfma.hpp)
-        const uint64_t nch = Q / zk::kDMQuads;
-        const uint32_t res = grid_for(c, nch * zk::kBlock, zk::k_gkr_dm<F>);
-        const uint32_t grid = step_grid(c, res, (nch + zk::kDMChunksMax - 1) / zk::kDMChunksMax);
-        launch(c, ZK_K_GKR_DM, bytes, muls, zk::k_gkr_dm<F>, grid, cur[0], cur[1], cur[2], cur[3], nx[0], nx[1],
-               nx[2], nx[3], Q, din, sk);
-        for (int t = 0; t < 4; ++t) cur[t] = nx[t];
-        enqueue_reduce(c, sk, across_ranks, zk::kDLimbs);
-        return;
-      }
-      const uint32_t grid = st.np == 2 ? grid_for(c, zk::kDQuads * Q, zk::k_gkr_dround<F, 2>)
-                                       : grid_for(c, zk::kDQuads * Q, zk::k_gkr_dround<F, 1>);
-      if (st.np == 2)
-        launch(c, ZK_K_GKR_DROUND, bytes, muls, zk::k_gkr_dround<F, 2>, grid, cur[0], cur[1], cur[2], cur[3], nx[0],
-               nx[1], nx[2], nx[3], Q, din, sk);
-      else
-        launch(c, ZK_K_GKR_DROUND, bytes, muls, zk::k_gkr_dround<F, 1>, grid, cur[0], cur[1], cur[2], cur[3], nx[0],
-               nx[1], nx[2], nx[3], Q, din, sk);
-      for (int t = 0; t < 4; ++t) cur[t] = nx[t];
-      enqueue_reduce(c, sk, across_ranks, zk::kDLimbs);
-      return;
-    }
-    // single round i: fold the previous level (size 2*size) by r_{i-1} and evaluate
+    const auto kern = st.dfs ? zk::k_gkr_dtail<F, true> : zk::k_gkr_dtail<F, false>;
+    launch(c, ZK_K_GKR_DTAIL, bytes, muls, kern, std::max<uint32_t>(grid, 1u), a, sinks[st.i]);
+    const uint64_t Ql = Q0 >> (2 * (st.nd - 1));
+    Fe* last = a.out + zk::dtail_region(Q0, st.nd - 1);
+    for (int t = 0; t < 4; ++t) cur[t] = last + (uint64_t)t * 4 * Ql;
+  }
+  void enqueue_double(size_t si) {  // input: level i - np (size << np), output: level i (size = 4Q)
+    const GStep& st = pl.steps[si];
+    const uint64_t size = ((uint64_t)1 << nv) >> st.i, Q = size / 4;
+    const zk::RoundSink& sk = sinks[st.i];
+    const bool two = st.np == 2;
+    const Fe z = zk::fe_zero<F>();
     Fe* nx[4];
     out_tables(size, nx);
-    zk::RoundIn rin{};
-    if (pre) {
-      rin.host = h_rin(c);
-      rin.relay = d_relay(c);
-      rin.err = h_err(c);
-      rin.tag = rtags[si] = ++c->rtag;
+    const zk::DIn din = make_din(c, pre, rtags[si], two ? rs.ra : z, rs.rb, two && !pre ? zk::fe_mul<F>(rs.ra, rs.rb) : z);
+    const double bytes = (two ? 2560.0 : 1536.0) * Q, muls = (two ? 40.0 : 24.0) * Q;
+    if (two && c->dm && Q >= std::max<uint64_t>(c->dm_min_quads, zk::kDMQuads)) {  // matrix cores (mfma.hpp)
+      const uint64_t nch = Q / zk::kDMQuads;
+      const uint32_t res = grid_for(c, nch * zk::kBlock, zk::k_gkr_dm<F>);
+      const uint32_t grid = step_grid(c, res, (nch + zk::kDMChunksMax - 1) / zk::kDMChunksMax);
+      launch(c, ZK_K_GKR_DM, bytes, muls, zk::k_gkr_dm<F>, grid, cur[0], cur[1], cur[2], cur[3], nx[0], nx[1], nx[2],
+             nx[3], Q, din, sk);
     } else {
-      rin.r = rb;
+      const auto kern = two ? zk::k_gkr_dround<F, 2> : zk::k_gkr_dround<F, 1>;
+      launch(c, ZK_K_GKR_DROUND, bytes, muls, kern, grid_for(c, zk::kDQuads * Q, kern), cur[0], cur[1], cur[2], cur[3],
+             nx[0], nx[1], nx[2], nx[3], Q, din, sk);
     }
+    wrote(nx, sk, zk::kDLimbs);
+  }
+  void enqueue_single(size_t si) {  // round i: fold the previous level (size 2*size) by r_{i-1} and evaluate
+    const uint32_t i = pl.steps[si].i;
+    const uint64_t size = ((uint64_t)1 << nv) >> i, h = size / 2;
+    const zk::RoundSink& sk = sinks[i];
+    Fe* nx[4];
+    out_tables(size, nx);
+    const zk::RoundIn rin = make_rin(c, pre, rtags[si], rs.rb);
     if (h <= c->lanes_max_pairs) {  // latency-bound size: 8 lanes per pair
       const uint32_t g8 = grid_for(c, 8 * h, zk::k_gkr_round_lanes<F>);
       launch(c, ZK_K_GKR_LANES, 768.0 * h, 12.0 * h, zk::k_gkr_round_lanes<F>, g8, cur[0], cur[1], cur[2], cur[3], nx[0], nx[1], nx[2], nx[3], h, rin, sk);
@@ -1281,335 +1018,218 @@ void gkr_phase(zk_ctx* c, const Fe* cur[4], uint32_t nv, uint32_t k0, bool acros
       const uint32_t grid = grid_for(c, 2 * h, zk::k_gkr_round<F>);
       launch(c, ZK_K_GKR_ROUND, 768.0 * h, 12.0 * h, zk::k_gkr_round<F>, grid, cur[0], cur[1], cur[2], cur[3], nx[0], nx[1], nx[2], nx[3], h, rin, sk);
     }
-    for (int t = 0; t < 4; ++t) cur[t] = nx[t];
-    enqueue_reduce(c, sk, across_ranks, 2 * 17);
-  };
-  // the highest challenge tag step si (and every step before it) waits for
-  auto last_tag = [&](size_t si) {
-    if (steps[si].kind == GS_TAIL) return rtags[si] + (nv - steps[si].i) - 1;
-    if (steps[si].kind == GS_DTAIL) return rtags[si] + steps[si].nd - 1;
-    return rtags[si];
-  };
-  PostR post{c};
-  if (pre) {
-    const auto t0 = std::chrono::steady_clock::now();
-    for (size_t si = 0; si < ns; ++si) {
-      enqueue(si);
-      post.last = last_tag(si);  // from here on the guard releases what is enqueued
+    wrote(nx, sk, 2 * 17);
+  }
+  void enqueue(size_t si) {
+    const GStep& st = pl.steps[si];
+    if (st.kind == GS_HOST) return;  // no kernel: the host runs these rounds
+    sinks[st.i] = make_sink(c, across_ranks);
+    if (c->block_trace && (int)si == c->block_trace_step) sinks[st.i].btrace = c->block_trace;
+    switch (st.kind) {
+      case GS_ROUND0: case GS_D0: case GS_D0T: return enqueue_input(st);
+      case GS_T32: case GS_T33: return enqueue_by_three(si);
+      case GS_TAIL: return enqueue_tail(si);
+      case GS_DTAIL: return enqueue_dtail(si);
+      case GS_DOUBLE: return enqueue_double(si);
+      default: return enqueue_single(si);
     }
-    if (getenv("ZK_DEBUG_ENQUEUE"))
-      fprintf(stderr, "zk: enqueued %zu steps (%u rounds) in %.1f us\n", ns, nv,
-              std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count());
+  }
+  // the highest challenge tag step si (and every step before it) waits for
+  uint32_t last_tag(size_t si) const {
+    const GStep& st = pl.steps[si];
+    return rtags[si] + (st.kind == GS_TAIL ? nv - st.i - 1 : (st.kind == GS_DTAIL ? st.nd - 1 : 0));
+  }
+
+  // a step's sums -> its rounds
+  void single(uint32_t i) {
+    Fe s2[2];
+    collect_sums<F, 2>(c, sinks[i], across_ranks, 17, s2);
+    later_round<F>(rs, i, s2[0], s2[1]);
+  }
+  void two(uint32_t i0) {
+    Fe d[zk::kDCats];
+    collect_sums<F, zk::kDCats>(c, sinks[i0], across_ranks, 17, d);
+    two_rounds<F>(rs, i0, false, d);
+  }
+  void three(uint32_t i0, bool first) {
+    Fe T[zk::kD0TCats];
+    collect_sums<F, zk::kD0TCats>(c, sinks[i0], across_ranks, 9, T, true);
+    three_rounds<F>(rs, i0, first, T);
+  }
+  void post_pair(uint32_t tag) { post.post2(rs.ra, rs.rb, zk::hfe_mul<F>(rs.ra, rs.rb), tag); }
+  void dtail(size_t si) {
+    const GStep& st = pl.steps[si];
+    const uint32_t last = st.i + 2 * (st.nd - 1);
+    if (!st.dfs) {
+      for (uint32_t d = 0; d < st.nd; ++d) {
+        two(st.i + 2 * d);
+        if (d + 1 < st.nd) post_pair(rtags[si] + d + 1);
+      }
+      return;
+    }
+    // device Fiat-Shamir: steps 0 .. nd-2 drew their own challenges; their
+    // records are complete once the last step's flag is up (every logging
+    // wave drained first, kernels.hpp k_gkr_dtail): replay them into the host
+    // transcript, then finish the last step
+    wait_flag(c, sinks[last].tag);
+    for (uint32_t d = 0; d + 1 < st.nd; ++d) {
+      const zk::FsLog& lg = c->h_fslog[d];
+      if (__atomic_load_n(&lg.tag, __ATOMIC_ACQUIRE) != rtags[si] + d) fail(ZK_EDEVICE, "device Fiat-Shamir record missing");
+      for (int j = 0; j < 2; ++j) {
+        if (const char* bad = replay_device_fs<F>(rs, st.i + 2 * d + j, lg.c[j], lg.m[j], lg.r[j])) fail(ZK_EDEVICE, bad);
+        c->stats.device_fs_rounds += 1;
+      }
+    }
+    two(last);
+  }
+  void host(const GStep& st) {
+    // the previous (persistent tail) step's output: level i - 2, 4 tables of
+    // 2^(H+2) in h_tab, complete once its flag was seen
+    const auto t0 = std::chrono::steady_clock::now();
+    // one bulk copy first: the device wrote these lines, so every host read
+    // misses; memcpy keeps many misses in flight, the unpack then hits L1
+    std::vector<uint64_t> raw((size_t)16 << (nv - st.i + 2));
+    memcpy(raw.data(), c->h_tab, raw.size() * 8);
+    const auto t1 = std::chrono::steady_clock::now();
+    host_rounds<F>(rs, st.i, nv, raw.data(), fin);
+    if (c->tail_trace)
+      fprintf(stderr, "zk host rounds %u..%u: %.2f us (table copy %.2f us)\n", st.i, nv - 1,
+              std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count(),
+              std::chrono::duration<double, std::micro>(t1 - t0).count());
+  }
+  // collects step si's sums and derives its rounds; returns how many of its
+  // challenges the tables it leaves have not been folded by
+  uint32_t derive(size_t si) {
+    const GStep& st = pl.steps[si];
+    switch (st.kind) {
+      case GS_ROUND0: {
+        Fe s3[3];
+        collect_sums<F, 3>(c, sinks[0], across_ranks, 17, s3);
+        one_round<F>(rs, 0, s3[0], s3[1], s3[2]);
+        return 1;
+      }
+      case GS_D0: {
+        Fe d[zk::kD0Cats];
+        collect_sums<F, zk::kD0Cats>(c, sinks[0], across_ranks, 17, d);
+        two_rounds<F>(rs, 0, true, d);
+        return 2;
+      }
+      case GS_D0T: case GS_T33: three(st.i, st.kind == GS_D0T); return 3;
+      case GS_T32: case GS_DOUBLE: two(st.i); return 2;
+      case GS_SINGLE: single(st.i); return 1;
+      case GS_TAIL:
+        for (uint32_t i = st.i; i < nv; ++i) {
+          single(i);
+          if (pre && i + 1 < nv) post.post(rs.r, rtags[si] + (i + 1 - st.i));
+        }
+        return 1;
+      case GS_HOST: host(st); return 0;
+      default: dtail(si); return 2;
+    }
   }
   // hand the newest challenge(s) to step si + 1
-  auto hand_on = [&](size_t si) {
-    if (!pre || si + 1 >= ns) return;
-    const GStep& nx = steps[si + 1];
+  void hand_on(size_t si) {
+    if (!pre || si + 1 >= pl.steps.size()) return;
+    const GStep& nx = pl.steps[si + 1];
+    const uint32_t tag = rtags[si + 1];
+    const Fe z = zk::fe_zero<F>();
     if (nx.kind == GS_HOST) return;
     if (nx.kind == GS_T32 || nx.kind == GS_T33) {
-      // eq((rz, ra, rb), c), c = 4a + 2b + c0 (rz, the oldest, on the top bit): the
-      // fold's eight weights, formed here instead of in every block of the step
-      // (five products: ab = eq((rz, ra), (a, b)) from rz ra by differences,
-      // then e(ab, c = 1) = ab rb and e(ab, c = 0) = ab - ab rb)
-      const Fe one = zk::fe_one<F>();
-      Fe ab[4];
-      ab[3] = zk::hfe_mul<F>(rz, ra);
-      ab[2] = zk::hfe_sub<F>(rz, ab[3]);                          // rz (1 - ra)
-      ab[1] = zk::hfe_sub<F>(ra, ab[3]);                          // (1 - rz) ra
-      ab[0] = zk::hfe_sub<F>(zk::hfe_sub<F>(one, rz), ab[1]);     // (1 - rz)(1 - ra)
       Fe e[8];
-      for (int q = 0; q < 4; ++q) {
-        e[2 * q + 1] = zk::hfe_mul<F>(ab[q], rb);
-        e[2 * q] = zk::hfe_sub<F>(ab[q], e[2 * q + 1]);
-      }
-      post.post8(e, rtags[si + 1]);
+      eq8_weights<F>(rs.rz, rs.ra, rs.rb, e);
+      post.post8(e, tag);
     } else if (nx.kind == GS_DTAIL && nx.dfs) {
       // the sponge after a challenge is the zero state + its 32-byte digest
       // buffered (dfs.hpp): the device continues the transcript from there
-      const zk::Keccak256& h = tr->h;
+      const zk::Keccak256& h = rs.tr->h;
       bool fresh = h.fill == 32;
       for (int q = 0; q < 25; ++q) fresh = fresh && h.st[q] == 0;
       if (!fresh) fail(ZK_EINVAL, "internal: device Fiat-Shamir needs a transcript right after a challenge");
       uint32_t dig[8];
       memcpy(dig, h.buf, 32);
-      const Fe rab = nx.np == 2 ? zk::hfe_mul<F>(ra, rb) : zk::fe_zero<F>();
-      post.post5(nx.np == 2 ? ra : zk::fe_zero<F>(), rb, rab, dig, claim, rtags[si + 1]);
+      const bool two = nx.np == 2;
+      post.post5(two ? rs.ra : z, rs.rb, two ? zk::hfe_mul<F>(rs.ra, rs.rb) : z, dig, rs.claim, tag);
     } else if (nx.kind == GS_DOUBLE || nx.kind == GS_DTAIL) {
       if (nx.np == 2)
-        post.post2(ra, rb, zk::hfe_mul<F>(ra, rb), rtags[si + 1]);
+        post_pair(tag);
       else
-        post.post2(zk::fe_zero<F>(), rb, zk::fe_zero<F>(), rtags[si + 1]);
+        post.post2(z, rs.rb, z, tag);
     } else {
-      post.post(rb, rtags[si + 1]);
+      post.post(rs.rb, tag);
     }
-  };
-  auto one_round = [&](uint32_t i, const Fe& e0, const Fe& e1, const Fe& e2) {
-    claim = finish_round<F>(tr, e0, e1, e2, k0 + i, out, r);
-    rz = ra;
-    ra = rb;
-    rb = r;
-  };
-  // rounds i0, i0 + 1, i0 + 2 from the 27 moment sums of k_gkr_d0t (tile id
-  // 9 alpha + 3 beta + gamma per axis: 0 = X0 Y0, 1 = X1 Y1, 2 = X0 Y1 + X1 Y0);
-  // X(t) Y(t) = (1-t)^2 m0 + t^2 m1 + t(1-t) ms, so at t = 2 the weights are (1, 4, -2)
-  auto three_rounds = [&](uint32_t i0, bool first) {
-    Fe T[zk::kD0TCats];
-    collect_sums<F, zk::kD0TCats>(c, sinks[i0], across_ranks, 9, T, true);
-    using namespace zk;
-    const Fe one = fe_one<F>();
-    auto at2w = [&](const Fe& m0, const Fe& m1, const Fe& ms) {  // value at t = 2: m0 + 4 m1 - 2 ms
-      const Fe m1x2 = hfe_add<F>(m1, m1);
-      return hfe_sub<F>(hfe_add<F>(m0, hfe_add<F>(m1x2, m1x2)), hfe_add<F>(ms, ms));
-    };
-    auto wts = [&](const Fe& t, Fe (&w)[3]) {  // (1-t)^2 = (1-t) - t(1-t), t(1-t) = t - t^2
-      w[1] = hfe_mul<F>(t, t);
-      w[2] = hfe_sub<F>(t, w[1]);
-      w[0] = hfe_sub<F>(hfe_sub<F>(one, t), w[2]);
-    };
-    Fe U[3];  // round i0: U[alpha] = sum over beta, gamma in {0, 1}
-    for (int a = 0; a < 3; ++a)
-      U[a] = hfe_add<F>(hfe_add<F>(T[9 * a], T[9 * a + 1]), hfe_add<F>(T[9 * a + 3], T[9 * a + 4]));
-    one_round(i0, U[0], first ? U[1] : hfe_sub<F>(claim, U[0]), at2w(U[0], U[1], U[2]));
-    Fe wa[3];
-    wts(r, wa);
-    Fe V[3];  // round i0 + 1: V[beta] = sum_alpha w(ra, alpha) sum_{gamma in {0, 1}}
-    for (int b = 0; b < 3; ++b) {
-      V[b] = fe_zero<F>();
-      for (int a = 0; a < 3; ++a)
-        V[b] = hfe_add<F>(V[b], hfe_mul<F>(wa[a], hfe_add<F>(T[9 * a + 3 * b], T[9 * a + 3 * b + 1])));
-    }
-    one_round(i0 + 1, V[0], hfe_sub<F>(claim, V[0]), at2w(V[0], V[1], V[2]));
-    Fe wb[3];
-    wts(r, wb);
-    Fe Z[3];  // round i0 + 2: Z[gamma] = sum_alpha w(ra, alpha) sum_beta w(rb, beta) T
-    for (int g = 0; g < 3; ++g) {
-      uint64_t acc[9] = {0};
-      for (int a = 0; a < 3; ++a) {
-        uint64_t in[9] = {0};
-        for (int b = 0; b < 3; ++b) h64::mac_wide(in, h64::of(wb[b]), h64::of(T[9 * a + 3 * b + g]));
-        h64::mac_wide(acc, h64::of(wa[a]), h64::of(wide_to_fe<F>(in)));
-      }
-      Z[g] = wide_to_fe<F>(acc);
-    }
-    one_round(i0 + 2, Z[0], hfe_sub<F>(claim, Z[0]), at2w(Z[0], Z[1], Z[2]));
-  };
-  // rounds i0 and i0 + 1 from a double step's eight product sums (the first
-  // step of a phase, k_gkr_d0: nine, the ninth V11 for round 0's e1)
-  auto two_rounds = [&](uint32_t i0, bool first = false) {
-      Fe d[zk::kD0Cats];
-      if (first)
-        collect_sums<F, zk::kD0Cats>(c, sinks[i0], across_ranks, 17, d);
-      else {
-        Fe d8[zk::kDCats];
-        collect_sums<F, zk::kDCats>(c, sinks[i0], across_ranks, 17, d8);
-        std::copy(d8, d8 + zk::kDCats, d);
-      }
-      // categories: 0 V00, 1 V22, 2 V01, 3 V02, 4 V10, 5 V20, 6 V21, 7 V12, 8 V11 (kernels.hpp)
-      // round i: e0 = V00 + V01, e1 = V10 + V11 (first) or s_{i-1}(r_{i-1}) - e0, e2 = V20 + V21
-      const Fe e0 = zk::hfe_add<F>(d[0], d[2]);
-      const Fe e1 = first ? zk::hfe_add<F>(d[4], d[8]) : zk::hfe_sub<F>(claim, e0);
-      one_round(i0, e0, e1, zk::hfe_add<F>(d[5], d[6]));
-      // round i + 1 at r = r_i: e0' through (V00, V10, V20), e2' through (V02, V12, V22) at r = 0, 1, 2
-      const Fe one = zk::fe_one<F>(), two = zk::hfe_add<F>(one, one);
-      const Fe rm1 = zk::hfe_sub<F>(r, one), rm2 = zk::hfe_sub<F>(r, two);
-      const Fe L0 = zk::hfe_half<F>(zk::hfe_mul<F>(rm1, rm2));                   // (r-1)(r-2)/2
-      const Fe L1 = zk::hfe_sub<F>(zk::fe_zero<F>(), zk::hfe_mul<F>(r, rm2));     // -r(r-2)
-      const Fe L2 = zk::hfe_half<F>(zk::hfe_mul<F>(r, rm1));                     // r(r-1)/2
-      auto lag = [&](const Fe& v0, const Fe& v1, const Fe& v2) {
-        return zk::hfe_add<F>(zk::hfe_add<F>(zk::hfe_mul<F>(L0, v0), zk::hfe_mul<F>(L1, v1)), zk::hfe_mul<F>(L2, v2));
-      };
-      const Fe f0 = lag(d[0], d[4], d[5]), f2 = lag(d[3], d[7], d[1]);
-      one_round(i0 + 1, f0, zk::hfe_sub<F>(claim, f0), f2);
-  };
+  }
+  void report() const;  // ZK_DEBUG_TAIL
+};
+
+// ZK_DEBUG_TAIL: kernel entry, challenge received, publish per step (block 0 /
+// last block), ZK_DEBUG_BLOCKS: per-block phases of one step, then the
+// persistent kernel's rounds.
+template <class F>
+void PhaseRun<F>::report() const {
+  const std::vector<GStep>& steps = pl.steps;
+  const size_t ns = steps.size();
+  HIPCK(hipStreamSynchronize(c->stream));
+  const uint64_t* S = c->tail_trace + 512;
+  uint64_t prev_pub = 0;
   for (size_t si = 0; si < ns; ++si) {
-    const GStep& st = steps[si];
-    if (!pre) enqueue(si);
-    if (st.kind == GS_ROUND0) {
-      Fe s3[3];
-      collect_sums<F, 3>(c, sinks[0], across_ranks, 17, s3);
-      one_round(0, s3[0], s3[1], s3[2]);
-      pend = 1;
-    } else if (st.kind == GS_D0) {
-      two_rounds(0, true);
-      pend = 2;
-    } else if (st.kind == GS_D0T) {
-      three_rounds(0, true);
-      pend = 3;
-    } else if (st.kind == GS_T32) {
-      two_rounds(st.i);
-      pend = 2;
-    } else if (st.kind == GS_T33) {
-      three_rounds(st.i, false);
-      pend = 3;
-    } else if (st.kind == GS_SINGLE) {
-      Fe s2[2];
-      collect_sums<F, 2>(c, sinks[st.i], across_ranks, 17, s2);
-      one_round(st.i, s2[0], zk::hfe_sub<F>(claim, s2[0]), s2[1]);
-      pend = 1;
-    } else if (st.kind == GS_TAIL) {
-      for (uint32_t i = st.i; i < nv; ++i) {
-        Fe s2[2];
-        collect_sums<F, 2>(c, sinks[i], across_ranks, 17, s2);
-        one_round(i, s2[0], zk::hfe_sub<F>(claim, s2[0]), s2[1]);
-        if (pre && i + 1 < nv) post.post(r, rtags[si] + (i + 1 - st.i));
-      }
-      pend = 1;
-    } else if (st.kind == GS_DOUBLE) {
-      two_rounds(st.i);
-      pend = 2;
-    } else if (st.kind == GS_HOST) {
-      // the previous (persistent tail) step's output: level i - 2, 4 tables of
-      // 2^(H+2) in h_tab, complete once its flag was seen; fold by r_{i-2}, r_{i-1}
-      const auto t0 = std::chrono::steady_clock::now();
-      const size_t len = (size_t)1 << (nv - st.i + 2);
-      // one bulk copy first: the device wrote these lines, so every host read
-      // misses; memcpy keeps many misses in flight, the unpack then hits L1
-      std::vector<uint64_t> raw((size_t)16 * len);
-      memcpy(raw.data(), c->h_tab, raw.size() * 8);
-      const auto t1 = std::chrono::steady_clock::now();
-      std::vector<Fe> T[4];
-      for (int t = 0; t < 4; ++t) {  // word-major per table (kernels.hpp st_fe_sys)
-        const uint64_t* w = raw.data() + (size_t)t * 4 * len;
-        T[t].resize(len);
-        for (size_t e = 0; e < len; ++e)
-          for (int k = 0; k < 4; ++k) {
-            const uint64_t x = w[k * len + e];
-            T[t][e].v[2 * k] = (uint32_t)x;
-            T[t][e].v[2 * k + 1] = (uint32_t)(x >> 32);
-          }
-      }
-      host_fold<F>(T, ra);
-      host_fold<F>(T, rb);
-      for (uint32_t i = st.i; i < nv; ++i) {
-        Fe e0, e2;
-        host_round_sums<F>(T, e0, e2);
-        one_round(i, e0, zk::hfe_sub<F>(claim, e0), e2);
-        if (i + 1 < nv || fin) host_fold<F>(T, r);
-      }
-      if (fin) {
-        for (int t = 0; t < 4; ++t) fin->v[t] = T[t][0];
-        fin->ok = true;
-      }
-      if (c->tail_trace)
-        fprintf(stderr, "zk host rounds %u..%u: %.2f us (table copy %.2f us)\n", st.i, nv - 1,
-                std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count(),
-                std::chrono::duration<double, std::micro>(t1 - t0).count());
-      pend = 0;
-    } else if (st.dfs) {  // GS_DTAIL, device Fiat-Shamir: steps 0 .. nd-2 drew their own challenges
-      // their records are complete once the last step's flag is up (every
-      // logging wave drained first, kernels.hpp k_gkr_dtail): replay them into
-      // the host transcript — absorb the device's coefficients, draw the
-      // challenge, check it against the device's — then finish the last step
-      wait_flag(c, sinks[st.i + 2 * (st.nd - 1)].tag);
-      for (uint32_t d = 0; d + 1 < st.nd; ++d) {
-        const zk::FsLog& lg = c->h_fslog[d];
-        if (__atomic_load_n(&lg.tag, __ATOMIC_ACQUIRE) != rtags[si] + d)
-          fail(ZK_EDEVICE, "device Fiat-Shamir record missing");
-        for (int j = 0; j < 2; ++j) {
-          Fe cf[3], rd;
-          for (int q = 0; q < 3; ++q) memcpy(cf[q].v, lg.c[j][q], 32);
-          memcpy(rd.v, lg.r[j], 32);
-          const uint32_t m = lg.m[j];
-          if (m > 3) fail(ZK_EDEVICE, "device Fiat-Shamir record corrupt");
-          for (uint32_t q = m; q < 3; ++q) cf[q] = zk::fe_zero<F>();
-          // the device's interpolation, checked: s(0) + s(1) = 2 c0 + c1 + c2 must be
-          // the running claim (a replayed hash alone proves only the replay)
-          const Fe s01 = zk::hfe_add<F>(zk::hfe_add<F>(zk::hfe_add<F>(cf[0], cf[0]), cf[1]), cf[2]);
-          if (memcmp(s01.v, claim.v, 32) != 0)
-            fail(ZK_EDEVICE, "device Fiat-Shamir round polynomial does not match the running claim");
-          const uint32_t k = k0 + st.i + 2 * d + j;
-          absorb<F>(tr, cf, m);
-          out.ncoeffs[k] = (uint8_t)m;
-          for (uint32_t q = 0; q < 3; ++q) out.coeffs[3 * k + q] = q < m ? cf[q] : zk::fe_zero<F>();
-          r = challenge<F>(tr);
-          if (memcmp(r.v, rd.v, 32) != 0) fail(ZK_EDEVICE, "device Fiat-Shamir challenge differs from the host transcript");
-          out.challenges[k] = r;
-          claim = zk::hfe_add<F>(cf[0], zk::hfe_mul<F>(r, zk::hfe_add<F>(cf[1], zk::hfe_mul<F>(r, cf[2]))));
-          c->stats.device_fs_rounds += 1;
-          rz = ra;
-          ra = rb;
-          rb = r;
+    if (steps[si].kind == GS_TAIL || steps[si].kind == GS_DTAIL || steps[si].kind == GS_HOST) break;
+    const uint64_t* row = S + (sinks[steps[si].i].tag & 63) * 4;
+    const bool first = steps[si].kind == GS_ROUND0 || steps[si].kind == GS_D0 || steps[si].kind == GS_D0T;  // no challenge to wait for
+    const uint64_t rr = first ? row[0] : row[1];
+    fprintf(stderr, "zk step %zu (kind %d, round %u): publish->entry %7.2f us, entry->r %7.2f, r->publish %8.2f"
+            " (r->block 0 loop end %8.2f, ->publish %6.2f)\n", si, steps[si].kind, steps[si].i,
+            prev_pub ? (row[0] - prev_pub) * 0.01 : 0.0, first ? 0.0 : (row[1] - row[0]) * 0.01, (row[2] - rr) * 0.01,
+            row[3] > rr ? (row[3] - rr) * 0.01 : 0.0, row[3] > rr ? ((int64_t)row[2] - (int64_t)row[3]) * 0.01 : 0.0);
+    prev_pub = row[2];
+    if (c->block_trace && (int)si == c->block_trace_step) {  // ZK_DEBUG_BLOCKS: per-block phases of this step
+      std::vector<double> le, ep, ci, fl, wd;
+      for (size_t b = 0; b < kBlockTraceMax; ++b) {
+        const uint64_t* q = c->block_trace + 8 * b;
+        if (!q[0] || !q[1] || !q[2]) continue;
+        le.push_back((double)((int64_t)q[0] - (int64_t)rr) * 0.01);
+        ep.push_back((double)((int64_t)q[1] - (int64_t)q[0]) * 0.01);
+        ci.push_back((double)((int64_t)q[2] - (int64_t)q[1]) * 0.01);
+        if (q[4] && q[5]) {
+          fl.push_back((double)((int64_t)q[4] - (int64_t)q[0]) * 0.01);
+          wd.push_back((double)((int64_t)q[5] - (int64_t)q[4]) * 0.01);
         }
       }
-      two_rounds(st.i + 2 * (st.nd - 1));
-      pend = 2;
-    } else {  // GS_DTAIL
-      for (uint32_t d = 0; d < st.nd; ++d) {
-        two_rounds(st.i + 2 * d);
-        if (d + 1 < st.nd) post.post2(ra, rb, zk::hfe_mul<F>(ra, rb), rtags[si] + d + 1);
-      }
-      pend = 2;
-    }
-    hand_on(si);
-  }
-  post.done = true;
-  if (c->tail_trace) {  // ZK_DEBUG_TAIL: kernel entry, challenge received, publish per step (block 0 / last block)
-    HIPCK(hipStreamSynchronize(c->stream));
-    const uint64_t* T = c->tail_trace + 512;
-    uint64_t prev_pub = 0;
-    for (size_t si = 0; si < ns; ++si) {
-      if (steps[si].kind == GS_TAIL || steps[si].kind == GS_DTAIL || steps[si].kind == GS_HOST) break;
-      const uint64_t* row = T + (sinks[steps[si].i].tag & 63) * 4;
-      const bool first = steps[si].kind == GS_ROUND0 || steps[si].kind == GS_D0 || steps[si].kind == GS_D0T;  // no challenge to wait for
-      const uint64_t rr = first ? row[0] : row[1];
-      fprintf(stderr, "zk step %zu (kind %d, round %u): publish->entry %7.2f us, entry->r %7.2f, r->publish %8.2f"
-              " (r->block 0 loop end %8.2f, ->publish %6.2f)\n", si, steps[si].kind, steps[si].i,
-              prev_pub ? (row[0] - prev_pub) * 0.01 : 0.0, first ? 0.0 : (row[1] - row[0]) * 0.01, (row[2] - rr) * 0.01,
-              row[3] > rr ? (row[3] - rr) * 0.01 : 0.0, row[3] > rr ? ((int64_t)row[2] - (int64_t)row[3]) * 0.01 : 0.0);
-      prev_pub = row[2];
-      if (c->block_trace && (int)si == c->block_trace_step) {  // ZK_DEBUG_BLOCKS: per-block phases of this step
-        std::vector<double> le, ep, ci, fl, wd;
-        for (size_t b = 0; b < kBlockTraceMax; ++b) {
-          const uint64_t* q = c->block_trace + 8 * b;
-          if (!q[0] || !q[1] || !q[2]) continue;
-          le.push_back((double)((int64_t)q[0] - (int64_t)rr) * 0.01);
-          ep.push_back((double)((int64_t)q[1] - (int64_t)q[0]) * 0.01);
-          ci.push_back((double)((int64_t)q[2] - (int64_t)q[1]) * 0.01);
-          if (q[4] && q[5]) {
-            fl.push_back((double)((int64_t)q[4] - (int64_t)q[0]) * 0.01);
-            wd.push_back((double)((int64_t)q[5] - (int64_t)q[4]) * 0.01);
+      auto pr = [](const char* what, std::vector<double> v) {
+        if (v.empty()) return;
+        std::sort(v.begin(), v.end());
+        fprintf(stderr, "    %-22s min %8.2f  p10 %8.2f  med %8.2f  p90 %8.2f  max %8.2f us (%zu blocks)\n", what, v.front(),
+                v[v.size() / 10], v[v.size() / 2], v[v.size() * 9 / 10], v.back(), v.size());
+      };
+      if (const char* fn = getenv("ZK_DEBUG_BLOCKS_FILE")) {  // raw per-block stamps (us after r)
+        if (FILE* f = fopen(fn, "w")) {
+          fprintf(f, "block,loop_end,fanin_start,counted_in\n");
+          for (size_t b = 0; b < kBlockTraceMax; ++b) {
+            const uint64_t* q = c->block_trace + 8 * b;
+            if (!q[0] || !q[1] || !q[2]) continue;
+            fprintf(f, "%zu,%.2f,%.2f,%.2f\n", b, ((int64_t)q[0] - (int64_t)rr) * 0.01, ((int64_t)q[1] - (int64_t)rr) * 0.01,
+                    ((int64_t)q[2] - (int64_t)rr) * 0.01);
           }
+          fclose(f);
         }
-        auto pr = [](const char* what, std::vector<double> v) {
-          if (v.empty()) return;
-          std::sort(v.begin(), v.end());
-          fprintf(stderr, "    %-22s min %8.2f  p10 %8.2f  med %8.2f  p90 %8.2f  max %8.2f us (%zu blocks)\n", what, v.front(),
-                  v[v.size() / 10], v[v.size() / 2], v[v.size() * 9 / 10], v.back(), v.size());
-        };
-        if (const char* fn = getenv("ZK_DEBUG_BLOCKS_FILE")) {  // raw per-block stamps (us after r)
-          if (FILE* f = fopen(fn, "w")) {
-            fprintf(f, "block,loop_end,fanin_start,counted_in\n");
-            for (size_t b = 0; b < kBlockTraceMax; ++b) {
-              const uint64_t* q = c->block_trace + 8 * b;
-              if (!q[0] || !q[1] || !q[2]) continue;
-              fprintf(f, "%zu,%.2f,%.2f,%.2f\n", b, ((int64_t)q[0] - (int64_t)rr) * 0.01, ((int64_t)q[1] - (int64_t)rr) * 0.01,
-                      ((int64_t)q[2] - (int64_t)rr) * 0.01);
-            }
-            fclose(f);
-          }
-        }
-        pr("r -> loop end", le);
-        pr("loop end -> epilogue", ep);
-        pr("epilogue -> counted in", ci);
-        pr("loop end -> flushed", fl);
-        pr("flushed -> words", wd);
-        memset(c->block_trace, 0, kBlockTraceMax * 64);
       }
+      pr("r -> loop end", le);
+      pr("loop end -> epilogue", ep);
+      pr("epilogue -> counted in", ci);
+      pr("loop end -> flushed", fl);
+      pr("flushed -> words", wd);
+      memset(c->block_trace, 0, kBlockTraceMax * 64);
     }
   }
-  if (c->tail_trace && !steps.empty() && steps.back().kind == GS_TAIL) {  // ZK_DEBUG_TAIL
-    HIPCK(hipStreamSynchronize(c->stream));
-    const uint64_t* T = c->tail_trace;
+  const uint64_t* T = c->tail_trace;
+  if (ns > 0 && steps.back().kind == GS_TAIL) {
     const uint32_t nr = nv - steps.back().i;
     for (uint32_t m = 0; m < nr; ++m)
       fprintf(stderr, "zk tail round %2u: wait r %6.2f us, fold+eval %6.2f, fan-in %6.2f, publish %6.2f, hand-off to next r %6.2f\n",
               m, (T[m * 8 + 1] - T[m * 8]) * 0.01, (T[m * 8 + 2] - T[m * 8 + 1]) * 0.01, (T[m * 8 + 3] - T[m * 8 + 2]) * 0.01,
               (T[m * 8 + 4] - T[m * 8 + 3]) * 0.01, m + 1 < nr ? (T[m * 8 + 9] - T[m * 8 + 4]) * 0.01 : 0.0);
   }
-  const size_t sdt = !steps.empty() && steps.back().kind == GS_HOST ? steps.size() - 2 : steps.size() - 1;
-  if (c->tail_trace && !steps.empty() && steps[sdt].kind == GS_DTAIL) {  // ZK_DEBUG_TAIL
-    HIPCK(hipStreamSynchronize(c->stream));
-    const uint64_t* T = c->tail_trace;
+  const size_t sdt = ns > 0 && steps.back().kind == GS_HOST ? ns - 2 : ns - 1;
+  if (ns > 0 && steps[sdt].kind == GS_DTAIL) {
     const uint32_t nd = steps[sdt].nd;
     for (uint32_t m = 0; m < nd; ++m)
       fprintf(stderr, "zk dtail step %u: wait r %6.2f us, fold+eval %6.2f, limb sums %6.2f, fan-in %6.2f, publish %6.2f, hand-off to next r %6.2f\n",
@@ -1620,6 +1240,48 @@ void gkr_phase(zk_ctx* c, const Fe* cur[4], uint32_t nv, uint32_t k0, bool acros
       fprintf(stderr, "zk dtail step %u fold+eval: constants %6.2f us, loop %6.2f, store drain %6.2f\n", m,
               (T[m * 8 + 6] - T[m * 8 + 1]) * 0.01, (T[m * 8 + 7] - T[m * 8 + 6]) * 0.01, (T[m * 8 + 2] - T[m * 8 + 7]) * 0.01);
   }
+}
+
+// Runs the phase: plan, buffers, every step enqueued up front (pre-enqueued)
+// or after its challenge, then per step its sums, its rounds and the hand-on.
+// gather_max > 0 (sharded phases): stop after the first step boundary b with
+// nv - b <= gather_max; *stop = b (nv when the phase runs to its end).
+// fin: filled (fin->ok) when the phase ends in host rounds — one more host
+// fold of the last two entries by the last challenge.
+// On return `cur` holds tables of 2^pend elements with the last `pend`
+// challenges not yet applied.
+template <class F>
+void gkr_phase(zk_ctx* c, const Fe* cur[4], uint32_t nv, uint32_t k0, bool across_ranks, zk_transcript* tr,
+               GkrOut& out, Fe& claim, Fe& r, uint32_t& pend, bool host_ok = false, uint32_t gather_max = 0,
+               uint32_t* stop = nullptr, FinalVals* fin = nullptr) {
+  if (fin) fin->ok = false;
+  const PlanKnobs knobs = plan_knobs(c, nv, across_ranks);
+  const PhasePlan plan = plan_phase(knobs, nv, host_ok, gather_max);
+  if (plan.error) fail(ZK_EINVAL, plan.error);
+  if (stop) *stop = plan.stop;
+  prepare_phase_buffers(c, plan);
+  const size_t ns = plan.steps.size();
+  const bool pre = knobs.pre;
+  const Fe z = zk::fe_zero<F>();
+  PhaseRun<F> run{c, cur, nv, across_ranks, pre, plan, fin, RoundState{tr, out, claim, r, k0, z, z, z},
+                  std::vector<zk::RoundSink>(nv), std::vector<uint32_t>(ns, 0), -1, PostR{c}};
+  if (pre) {
+    const auto t0 = std::chrono::steady_clock::now();
+    for (size_t si = 0; si < ns; ++si) {
+      run.enqueue(si);
+      run.post.last = run.last_tag(si);  // from here on the guard releases what is enqueued
+    }
+    if (getenv("ZK_DEBUG_ENQUEUE"))
+      fprintf(stderr, "zk: enqueued %zu steps (%u rounds) in %.1f us\n", ns, nv,
+              std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count());
+  }
+  for (size_t si = 0; si < ns; ++si) {
+    if (!pre) run.enqueue(si);
+    pend = run.derive(si);
+    run.hand_on(si);
+  }
+  run.post.done = true;
+  if (c->tail_trace) run.report();
 }
 
 template <class F>
@@ -1796,14 +1458,7 @@ void sc_prove_device(zk_ctx* c, const Fe* dX, uint32_t n, zk_transcript* tr, con
     const uint64_t h = (N >> k) / 2;
     const uint32_t grid = grid_for(c, h, zk::k_sc_round<F, false>);
     Fe* nx = c->work[(k + 1) & 1].fe();
-    if (pre) {
-      rin.host = h_rin(c);
-      rin.relay = d_relay(c);
-      rin.err = h_err(c);
-      rin.tag = rtags[k] = ++c->rtag;
-    } else {
-      rin.r = r;
-    }
+    rin = make_rin(c, pre, rtags[k], r);
     launch(c, ZK_K_SC_ROUND, 192.0 * h, 2.0 * h, zk::k_sc_round<F, false>, grid, cur, nx, h, rin, sinks[k]);
     cur = nx;
   };

@@ -10,6 +10,7 @@
 #pragma once
 #include "field.hpp"
 #include "dfs.hpp"
+#include "gkr_plan.hpp"  // tail_region, dtail_region
 
 namespace zk {
 
@@ -818,8 +819,6 @@ __device__ __forceinline__ void st_fe_a(Fe* p, uint64_t i, const Fe& x) {
                        __HIP_MEMORY_SCOPE_AGENT);
 }
 
-__host__ __device__ __forceinline__ uint64_t tail_region(uint64_t h0, uint32_t m) { return 8 * (h0 - (h0 >> m)); }
-
 template <class F>
 __global__ __launch_bounds__(kBlock) void k_gkr_tail(TailArgs a, RoundSink sink) {
   __shared__ LimbScratch<17> sc;
@@ -1189,11 +1188,6 @@ struct DTailArgs {
   uint64_t* host_tab; // pinned host memory: the last step's 4 output tables (16 Q elements), or null (host-side rounds)
   FsLog* fslog;       // (DFS) pinned: per step but the last, the rounds the device drew (dfs.hpp)
 };
-__host__ __device__ __forceinline__ uint64_t dtail_region(uint64_t Q0, uint32_t s) {
-  uint64_t o = 0;
-  for (uint32_t t = 0; t < s; ++t) o += 16 * (Q0 >> (2 * t));
-  return o;
-}
 
 // The last device step (host_tab set) stores its output tables to pinned host
 // memory instead, with system-scope stores, word-major per table (word k of
