@@ -243,12 +243,6 @@ ZK_HD void wide_mac(Wide& acc, const Fe& a, const Fe& b) {
   for (int k = 0; k < 16; ++k) acc.w[k] = addc32(acc.w[k], t[k], c, &c);
   acc.w[16] += c;
 }
-template <class F>
-ZK_HD void wide_add(Wide& acc, const Wide& x) {
-  uint32_t c = 0;
-#pragma unroll
-  for (int k = 0; k < 17; ++k) acc.w[k] = addc32(acc.w[k], x.w[k], c, &c);
-}
 // REDC of a 544-bit value: V * 2^-256 mod p, fully reduced
 template <class F>
 ZK_HD Fe wide_redc(const Wide& V) {

@@ -82,6 +82,52 @@ __device__ __forceinline__ void st_row(uint8_t* row, const Fe& x) {
   d[1] = make_uint4(x.v[4], x.v[5], x.v[6], x.v[7]);
 }
 
+// Wave w's table of a step over the four tables (w = 0 .. 3: A, S, M, P). One
+// select per statement: as one nested conditional, the input and the output
+// table's calls merged into a switch over w, and k_gkr_dm3 (246 VGPRs) spilled.
+template <class T>
+__device__ __forceinline__ T* table_of(uint32_t w, T* A, T* S, T* M, T* P) {
+  T* r = w == 2 ? M : P;
+  r = w == 1 ? S : r;
+  return w == 0 ? A : r;
+}
+
+template <int N>
+__device__ __forceinline__ void zero_tiles(i32x16 (&acc)[N]) {
+#pragma unroll
+  for (int i = 0; i < N; ++i)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[i][r] = 0;
+}
+
+// A block's sum state behind its digit images (Image: a struct with the
+// kernel's img, 16-byte rows; first in LDS, so every row stays aligned): the
+// anti-diagonal sums (digit position k + l) of NT categories as int64, and
+// what grid_finish works in.
+template <class Image, int NT>
+struct SumScratch : Image {
+  unsigned long long T[NT][64];
+  uint64_t tot[kSlotU64];
+  uint64_t pp[kBlock];
+  uint32_t am_last;
+};
+
+// a wave's int32 tiles acc[0..N) into the sums of categories cat0 .. cat0 + N - 1
+// (T zeroed before a barrier): register r of lane (col, h) is row
+// (r & 3) + 8 (r >> 2) + 4 h, column col of the 32 x 32 tile
+template <int N, int NT>
+__device__ __forceinline__ void flush_tiles(const i32x16 (&acc)[N], uint32_t cat0, unsigned long long (&T)[NT][64]) {
+  const uint32_t l = threadIdx.x & 63, col = l & 31, h = l >> 5;
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const uint32_t row = (r & 3) + 8 * (r >> 2) + 4 * h;
+      atomicAdd(&T[cat0 + i][row + col], (unsigned long long)(long long)acc[i][r]);
+    }
+  }
+}
+
 // ---------------------------------------------------------------------------
 // k_gkr_d0m: rounds 0 and 1 from the input tables in one pass (the step of
 // the removed VALU k_gkr_d0r: nine categories, limb-sum output) with the products on
@@ -104,13 +150,10 @@ __device__ __forceinline__ void st_row(uint8_t* row, const Fe& x) {
 constexpr uint32_t kD0MChunksMax = 2048;  // chunks of 32 quads per wave (int32 tile bound: 1 MFMA per chunk)
 static_assert(1ull * (1u << 19) * kD0MChunksMax <= (1ull << 30), "d0m tile bound");
 constexpr int kD0MPts = 5;                // point images per phase
-struct D0MScratch {
-  uint8_t img[4][kD0MPts][2][32][32];   // per wave: point, table (X, Y), 32 rows of 32 bytes
-  unsigned long long T[kD0Cats][64];    // anti-diagonal sums per category (int64)
-  uint64_t tot[kSlotU64];
-  uint64_t pp[kBlock];
-  uint32_t am_last;
+struct D0MImage {
+  uint8_t img[4][kD0MPts][2][32][32];  // per wave: point, table (X, Y), 32 rows of 32 bytes
 };
+using D0MScratch = SumScratch<D0MImage, kD0Cats>;
 
 // write the digit images of NP values and accumulate one MFMA per value
 template <int NP>
@@ -155,6 +198,46 @@ __device__ __forceinline__ uint32_t d0m_offset_word(int w) {
   return lo | hi;
 }
 
+// G + M -> 17 words for each of NT categories, by the block (a per-category
+// serial chain took ~1.5 us on one wave): (tile, word) items build
+// S_w = sum_{i<4} T[4w+i] 2^(8i) (|T| < 2^37: |S_w| < 2^62), NT threads run
+// the 17-step signed carries in place. Ends on a barrier.
+template <class F, int NT>
+__device__ __forceinline__ void tiles_to_words(const unsigned long long (&T)[NT][64], uint64_t (&W)[NT][17]) {
+  for (uint32_t it = threadIdx.x; it < (uint32_t)NT * 17; it += kBlock) {
+    const uint32_t tile = it / 17, w = it % 17;
+    int64_t v = 0;
+#pragma unroll
+    for (uint32_t i = 0; i < 4; ++i)
+      if (4 * w + i < 63) v += (int64_t)T[tile][4 * w + i] * ((int64_t)1 << (8 * i));
+    W[tile][w] = (uint64_t)v;
+  }
+  __syncthreads();
+  if (threadIdx.x < (uint32_t)NT) {
+    int64_t carry = 0;
+#pragma unroll
+    for (int w = 0; w < 17; ++w) {
+      const int64_t v = (int64_t)W[threadIdx.x][w] + (int64_t)d0m_offset_word<F>(w) + carry;
+      W[threadIdx.x][w] = (uint32_t)v;
+      carry = v >> 32;
+    }
+  }
+  __syncthreads();
+}
+
+// Epilogue of k_gkr_d0m, k_gkr_dm and k_gkr_dm3 (NT = 9 or 8 categories, the
+// wave's tiles being categories cat0 ..): tiles -> anti-diagonal sums -> 17
+// words per category, the limb sums as they stand -> grid limb sums
+template <class F, int N, class Img, int NT>
+__device__ __forceinline__ void sum_epilogue(const i32x16 (&acc)[N], uint32_t cat0, SumScratch<Img, NT>& sc,
+                                             const RoundSink& sink) {
+  static_assert(NT * 17 <= kSlotU64, "a slot holds the categories' words");
+  flush_tiles(acc, cat0, sc.T);
+  __syncthreads();
+  tiles_to_words<F, NT>(sc.T, *reinterpret_cast<uint64_t(*)[NT][17]>(sc.tot));
+  grid_finish<NT * 17>(sc, sink);
+}
+
 template <class F>
 __global__ __launch_bounds__(kBlock, 2) void k_gkr_d0m(const Fe* __restrict__ A, const Fe* __restrict__ S,
                                                       const Fe* __restrict__ M, const Fe* __restrict__ P, uint64_t Q,
@@ -165,10 +248,7 @@ __global__ __launch_bounds__(kBlock, 2) void k_gkr_d0m(const Fe* __restrict__ A,
   for (uint32_t i = t; i < kD0Cats * 64; i += kBlock) (&sc.T[0][0])[i] = 0;
   // tiles in category order: 0 V00, 1 V22, 2 V01, 3 V02, 4 V10, 5 V20, 6 V21, 7 V12, 8 V11
   i32x16 acc[kD0Cats];
-#pragma unroll
-  for (int i = 0; i < kD0Cats; ++i)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[i][r] = 0;
+  zero_tiles(acc);
   const Fe* __restrict__ T = (l >> 5) ? (pp ? P : S) : (pp ? M : A);
   const uint64_t nch = (Q + 31) / 32, stride = (uint64_t)gridDim.x * 2;
   uint64_t ch = (uint64_t)blockIdx.x * 2 + (w >> 1);
@@ -201,35 +281,8 @@ __global__ __launch_bounds__(kBlock, 2) void k_gkr_d0m(const Fe* __restrict__ A,
     }
   }
   __syncthreads();  // T zeroed
-  const uint32_t col = l & 31, h = l >> 5;
-#pragma unroll
-  for (int i = 0; i < kD0Cats; ++i) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const uint32_t row = (r & 3) + 8 * (r >> 2) + 4 * h;
-      atomicAdd(&sc.T[i][row + col], (unsigned long long)(long long)acc[i][r]);
-    }
-  }
-  __syncthreads();
-  if (t < (uint32_t)kD0Cats) {  // G + M -> 17 words, signed byte-wise carry
-    int64_t carry = 0;
-    uint32_t word = 0;
-    for (int d = 0; d < 68; ++d) {
-      const int wd = d >> 2, sh = 8 * (d & 3);
-      int64_t s = carry + (d < 63 ? (int64_t)sc.T[t][d] : 0);
-      s += (int64_t)((d0m_offset_word<F>(wd) >> sh) & 0xffu);
-      word |= (uint32_t)(s & 0xff) << sh;
-      carry = s >> 8;
-      if ((d & 3) == 3) {
-        sc.tot[t * 17 + wd] = word;
-        word = 0;
-      }
-    }
-  }
-  __syncthreads();
-  grid_finish<kD0Limbs>(sc, sink);
+  sum_epilogue<F>(acc, 0, sc, sink);
 }
-
 
 // ---------------------------------------------------------------------------
 // Double steps on the matrix cores: k_gkr_dm (two pending challenges).
@@ -464,42 +517,16 @@ __device__ __forceinline__ Fe dm_fold(const Fe (&x)[4], const i32x4 (&wf)[3]) {
 constexpr uint32_t kDMQuads = 64;        // quads per chunk (one per lane)
 constexpr uint32_t kDMChunksMax = 1024;  // chunks per block (int32 product tiles: 2 MFMAs, 2^20 per chunk)
 static_assert(2ull * (1u << 19) * kDMChunksMax <= (1ull << 30), "dm tile bound");
-struct DMScratch {
+struct DMImage {
   uint8_t img[kDCats][4][kDMQuads][32];  // 64 KB: category, table, quad, digit row
   uint8_t wimg[3][32][32];                // digit rows of the fold constants (c, k)
-  unsigned long long T[kDCats][64];
-  uint64_t tot[kSlotU64];
-  uint64_t pp[kBlock];
-  uint32_t am_last;
 };
+using DMScratch = SumScratch<DMImage, kDCats>;
 
 template <class F>
 __device__ __forceinline__ void dm_row(uint8_t (&row)[32], Fe x) {
   to_digits(x);
   st_row(row, x);
-}
-
-// G + M -> 17 words for category t (threads < ncat), as k_gkr_d0m
-template <class F>
-__device__ __forceinline__ void diag_to_words(const unsigned long long (&T)[64], uint64_t* out) {
-  // word w of G: S_w = sum_{i<4} T[4w+i] 2^(8i) (|T| < 2^37: |S_w| < 2^62), then one
-  // signed carry chain over the 17 words (fully unrolled: the LDS reads issue up front)
-  int64_t S[17];
-#pragma unroll
-  for (int w = 0; w < 17; ++w) {
-    int64_t v = 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      if (4 * w + i < 63) v += (int64_t)T[4 * w + i] * ((int64_t)1 << (8 * i));
-    S[w] = v;
-  }
-  int64_t carry = 0;
-#pragma unroll
-  for (int w = 0; w < 17; ++w) {
-    const int64_t v = S[w] + (int64_t)d0m_offset_word<F>(w) + carry;
-    out[w] = (uint32_t)v;
-    carry = v >> 32;
-  }
 }
 
 // The eight grid-point values of the quad whose folded corners z[0..3] this
@@ -531,27 +558,6 @@ __device__ __forceinline__ void dm_products(const Fe (&z)[4], DMScratch& sc, i32
   }
   __syncthreads();
 }
-template <class F, int NT>
-__device__ __forceinline__ void tiles_to_words(const unsigned long long (&T)[NT][64], uint64_t (&W)[NT][17]);
-
-// tiles -> anti-diagonal sums -> 17 words per category -> grid limb sums
-template <class F>
-__device__ __forceinline__ void dm_epilogue(const i32x16 (&acc)[4], DMScratch& sc, const RoundSink& sink) {
-  const uint32_t t = threadIdx.x;
-  const uint32_t l = t & 63, cg = t >> 7, col = l & 31, h = l >> 5;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const uint32_t row = (r & 3) + 8 * (r >> 2) + 4 * h;
-      atomicAdd(&sc.T[4 * cg + i][row + col], (unsigned long long)(long long)acc[i][r]);
-    }
-  }
-  __syncthreads();
-  tiles_to_words<F, kDCats>(sc.T, *reinterpret_cast<uint64_t(*)[kDCats][17]>(sc.tot));
-  __syncthreads();
-  grid_finish<kDLimbs>(sc, sink);
-}
 
 template <class F>
 __global__ __launch_bounds__(kBlock, 2) void k_gkr_dm(const Fe* __restrict__ A, const Fe* __restrict__ S,
@@ -573,13 +579,10 @@ __global__ __launch_bounds__(kBlock, 2) void k_gkr_dm(const Fe* __restrict__ A, 
   i32x4 wf[3];
 #pragma unroll
   for (int c = 0; c < 3; ++c) wf[c] = tr_frag(&sc.wimg[c][0][0]);
-  const Fe* __restrict__ X = w == 0 ? A : (w == 1 ? S : (w == 2 ? M : P));
-  Fe* __restrict__ X2 = w == 0 ? A2 : (w == 1 ? S2 : (w == 2 ? M2 : P2));
+  const Fe* __restrict__ X = table_of(w, A, S, M, P);
+  Fe* __restrict__ X2 = table_of(w, A2, S2, M2, P2);
   i32x16 acc[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[i][r] = 0;
+  zero_tiles(acc);
   const uint64_t nch = Q / kDMQuads, h4 = 4 * Q;
   Fe in[4];  // inputs of the next fold, loaded one fold ahead
   if ((uint64_t)blockIdx.x < nch) dm_load(X, (uint64_t)blockIdx.x * kDMQuads + l, h4, in);
@@ -603,7 +606,7 @@ __global__ __launch_bounds__(kBlock, 2) void k_gkr_dm(const Fe* __restrict__ A, 
   }
   if (blockIdx.x == 0) ZK_SINK_STAMP(sink, 3);  // block 0 leaves its main loop
   ZK_BLOCK_STAMP(sink, 0);
-  dm_epilogue<F>(acc, sc, sink);
+  sum_epilogue<F>(acc, 4 * (w >> 1), sc, sink);
 }
 
 
@@ -649,68 +652,16 @@ static __constant__ Fe kP2WBn254Fr[9] = ZK_P2W_INIT(Bn254Fr);
 static __constant__ Fe kP2WBn254Fq[9] = ZK_P2W_INIT(Bn254Fq);
 static __constant__ Fe kP2WBls12_381Fr[9] = ZK_P2W_INIT(Bls12_381Fr);
 template <class F>
-__device__ __forceinline__ Fe p2w(uint32_t k) {  // 2^(32 (8 + k)) mod p
-  if constexpr (F::id == BN254_FR) return kP2WBn254Fr[k];
-  else if constexpr (F::id == BN254_FQ) return kP2WBn254Fq[k];
-  else return kP2WBls12_381Fr[k];
-}
-template <class F>
 __device__ __forceinline__ uint32_t p2w_word(uint32_t k, uint32_t j) {  // word j of 2^(32 (8 + k)) mod p (dynamic j)
   if constexpr (F::id == BN254_FR) return kP2WBn254Fr[k].v[j];
   else if constexpr (F::id == BN254_FQ) return kP2WBn254Fq[k].v[j];
   else return kP2WBls12_381Fr[k].v[j];
 }
 template <class F>
-__device__ __forceinline__ void words17_to_limbs9(const uint64_t* x, uint64_t* out) {
-  uint64_t col[9];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) col[j] = x[j];
-  col[8] = 0;
-#pragma unroll
-  for (int w = 8; w < 17; ++w) {
-    const Fe k = p2w<F>(w - 8);
-    const uint32_t xw = (uint32_t)x[w];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const uint64_t pr = (uint64_t)xw * k.v[j];
-      col[j] += (uint32_t)pr;
-      col[j + 1] += pr >> 32;
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < 9; ++j) out[j] = col[j];
-}
-
-// Block-parallel epilogue of NT tiles (the per-tile serial chains of
-// diag_to_words / words17_to_limbs9 took ~1.5 us each on one wave):
-// (tile, word) items build S_w, NT threads run the 17-step carries in place,
-// (tile, limb) items fold the high words (2 products per high word each).
-template <class F, int NT>
-__device__ __forceinline__ void tiles_to_words(const unsigned long long (&T)[NT][64], uint64_t (&W)[NT][17]) {
-  for (uint32_t it = threadIdx.x; it < (uint32_t)NT * 17; it += kBlock) {
-    const uint32_t tile = it / 17, w = it % 17;
-    int64_t v = 0;
-#pragma unroll
-    for (uint32_t i = 0; i < 4; ++i)
-      if (4 * w + i < 63) v += (int64_t)T[tile][4 * w + i] * ((int64_t)1 << (8 * i));
-    W[tile][w] = (uint64_t)v;
-  }
-  __syncthreads();
-  if (threadIdx.x < (uint32_t)NT) {
-    int64_t carry = 0;
-#pragma unroll
-    for (int w = 0; w < 17; ++w) {
-      const int64_t v = (int64_t)W[threadIdx.x][w] + (int64_t)d0m_offset_word<F>(w) + carry;
-      W[threadIdx.x][w] = (uint32_t)v;
-      carry = v >> 32;
-    }
-  }
-  __syncthreads();
-}
-template <class F>
 __device__ __forceinline__ void stage_p2w(uint32_t (&K)[9][8]) {  // threads < 72; read after a barrier
   if (threadIdx.x < 72) K[threadIdx.x >> 3][threadIdx.x & 7] = p2w_word<F>(threadIdx.x >> 3, threadIdx.x & 7);
 }
+// by the block, as tiles_to_words: (tile, limb) items fold the high words (2 products per high word each)
 template <class F, int NT>
 __device__ __forceinline__ void words_to_limbs9(const uint64_t (&W)[NT][17], const uint32_t (&K)[9][8], uint64_t* tot) {
   for (uint32_t it = threadIdx.x; it < (uint32_t)NT * 9; it += kBlock) {
@@ -726,24 +677,29 @@ __device__ __forceinline__ void words_to_limbs9(const uint64_t (&W)[NT][17], con
   }
 }
 
-struct D0TScratch {
-  uint8_t img[2][8][2][32][32];  // buffer, corner, table (X, Y), octant, digit row (32 KiB)
-  unsigned long long T[kD0TCats][64];
+// the sum state of the 27 moment tiles (k_gkr_d0t, k_gkr_t33)
+template <class Image>
+struct MomentScratch : SumScratch<Image, kD0TCats> {
   uint64_t w17[kD0TCats][17];
-  uint64_t tot[kSlotU64];
-  uint64_t pp[kBlock];
-  uint32_t am_last;
   uint32_t p2w[9][8];  // 2^(32 (8 + k)) mod p, staged at kernel start for words_to_limbs9
 };
+struct D0TImage {
+  uint8_t img[2][8][2][32][32];  // buffer, corner, table (X, Y), octant, digit row (32 KiB)
+};
+using D0TScratch = MomentScratch<D0TImage>;
 
-// wave w = 2 aX + aY: products X_u Y_v, u = 4 aX + ux, v = 4 aY + vy; tile slot 3 d_b + d_c
-__device__ __forceinline__ void d0t_mfmas(const uint8_t (*img)[2][32][32], i32x16 (&acc)[9]) {
+// Wave w = 2 aX + aY: the 16 products X_u Y_v, u = 4 aX + ux, v = 4 aY + vy,
+// over 32 octants (rows r0 .. r0 + 31 of tables tX and tY of an image
+// [corner][table][octant][digit row]) into tile slot 3 d_b + d_c
+template <int NTAB, int NOCT>
+__device__ __forceinline__ void moment_products(const uint8_t (&img)[8][NTAB][NOCT][32], uint32_t tX, uint32_t tY,
+                                                uint32_t r0, i32x16 (&acc)[9]) {
   const uint32_t w = threadIdx.x >> 6, aX = w >> 1, aY = w & 1;
   i32x4 fa[4], fb[4];
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
-    fa[k] = tr_frag(&img[4 * aX + k][0][0][0]);
-    fb[k] = tr_frag(&img[4 * aY + k][1][0][0]);
+    fa[k] = tr_frag(&img[4 * aX + k][tX][r0][0]);
+    fb[k] = tr_frag(&img[4 * aY + k][tY][r0][0]);
   }
 #pragma unroll
   for (int ux = 0; ux < 4; ++ux)
@@ -753,17 +709,23 @@ __device__ __forceinline__ void d0t_mfmas(const uint8_t (*img)[2][32][32], i32x1
       acc[slot] = __builtin_amdgcn_mfma_i32_32x32x32_i8(fa[ux], fb[vy], acc[slot], 0, 0, 0);
     }
 }
-__device__ __forceinline__ void d0t_flush(const i32x16 (&acc)[9], unsigned long long (&T)[kD0TCats][64]) {
-  const uint32_t w = threadIdx.x >> 6, l = threadIdx.x & 63, col = l & 31, h = l >> 5;
-  const uint32_t da = (uint32_t)moment_digit((int)(w >> 1), (int)(w & 1));
-#pragma unroll
-  for (int i = 0; i < 9; ++i) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const uint32_t row = (r & 3) + 8 * (r >> 2) + 4 * h;
-      atomicAdd(&T[9 * da + i][row + col], (unsigned long long)(long long)acc[i][r]);
-    }
-  }
+
+// A moment kernel's end: the waves' tiles (wave w = 2 aX + aY holds the nine
+// of variable-0 moment d_a) -> anti-diagonal sums -> 17 words -> 9 limb sums
+// per tile -> grid limb sums. STAMPS: k_gkr_t33's block trace slots 4 and 5.
+template <class F, bool STAMPS = false, class Image>
+__device__ __forceinline__ void moment_epilogue(const i32x16 (&acc)[9], MomentScratch<Image>& sc,
+                                                const RoundSink& sink) {
+  const uint32_t w = threadIdx.x >> 6;
+  __syncthreads();
+  flush_tiles(acc, 9 * (uint32_t)moment_digit((int)(w >> 1), (int)(w & 1)), sc.T);
+  __syncthreads();
+  if constexpr (STAMPS) ZK_BLOCK_STAMP(sink, 4);
+  tiles_to_words<F, kD0TCats>(sc.T, sc.w17);
+  if constexpr (STAMPS) ZK_BLOCK_STAMP(sink, 5);
+  words_to_limbs9<F, kD0TCats>(sc.w17, sc.p2w, sc.tot);
+  __syncthreads();
+  grid_finish<kD0TLimbs>(sc, sink);
 }
 
 // order 2: the groups themselves in the order t33_group_perm, so that the
@@ -799,10 +761,7 @@ __global__ __launch_bounds__(kBlock, 2) void k_gkr_d0t(const Fe* __restrict__ A,
   for (uint32_t i = t; i < kD0TCats * 64; i += kBlock) (&sc.T[0][0])[i] = 0;
   stage_p2w<F>(sc.p2w);
   i32x16 acc[9];
-#pragma unroll
-  for (int i = 0; i < 9; ++i)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[i][r] = 0;
+  zero_tiles(acc);
   const uint32_t pp = blockIdx.x & 1;
   const Fe* __restrict__ T = half ? (pp ? P : S) : (pp ? M : A);
   const uint64_t nch = O / 32, nb = gridDim.x >> 1;
@@ -860,17 +819,11 @@ __global__ __launch_bounds__(kBlock, 2) void k_gkr_d0t(const Fe* __restrict__ A,
       if (ch + nb < nch) load(ch + nb);  // the next chunk's corners, in flight during this chunk's products
     }
     __syncthreads();  // the image of this chunk is complete (double buffering: one barrier per chunk)
-    d0t_mfmas(sc.img[buf], acc);
+    moment_products(sc.img[buf], 0, 1, 0, acc);
   }
   if (blockIdx.x == 0) ZK_SINK_STAMP(sink, 3);  // block 0 leaves its main loop
   ZK_BLOCK_STAMP(sink, 0);
-  __syncthreads();
-  d0t_flush(acc, sc.T);
-  __syncthreads();
-  tiles_to_words<F, kD0TCats>(sc.T, sc.w17);
-  words_to_limbs9<F, kD0TCats>(sc.w17, sc.p2w, sc.tot);
-  __syncthreads();
-  grid_finish<kD0TLimbs>(sc, sink);
+  moment_epilogue<F>(acc, sc, sink);
 }
 
 
@@ -888,8 +841,36 @@ __global__ __launch_bounds__(kBlock, 2) void k_gkr_d0t(const Fe* __restrict__ A,
 struct DM3Scratch : DMScratch {
   Fe eqw[8];
 };
-// 8 inputs of a fold (weights wf[0..7]) into its two MFMA accumulators
-__device__ __forceinline__ void fold_acc8(Fe (&x)[8], const i32x4* wf, i32x16& acc0, i32x16& acc1) {
+// The eight weights' A fragments wf of a fold by three challenges: eq(r, c)
+// (the oldest pending challenge on c's top bit) as posted or formed into eqw, the
+// digit rows of eq(r, c) 2^(8k + 64) into `borrowed` (an image the kernel
+// fills later: the rows are dead once their fragments are in registers, after
+// the last barrier here). arrived() runs once the challenges are in, before
+// any barrier.
+template <class F, class Image, class Arrived>
+__device__ __forceinline__ void eq8_fragments(const DIn& din, Fe (&eqw)[8], Image& borrowed, i32x4 (&wf)[8],
+                                              Arrived&& arrived) {
+  static_assert(sizeof(Image) >= 8 * 32 * 32 && kBlock == 8 * 32, "a digit row per thread");
+  const uint32_t t = threadIdx.x;
+  block_get_eq8<F>(din, eqw, gridDim.x > 1);
+  arrived();
+  __syncthreads();
+  uint8_t(*wimg)[32][32] = reinterpret_cast<uint8_t(*)[32][32]>(&borrowed);
+  dm_row<F>(wimg[t >> 5][t & 31], fe_mul<F>(eqw[t >> 5], p2dig<F>(t & 31)));
+  __syncthreads();
+#pragma unroll
+  for (int c = 0; c < 8; ++c) wf[c] = tr_frag(&wimg[c][0][0]);
+  __syncthreads();
+}
+
+// One output of the fold: its eight inputs by the weights wf[0..7] (one K = 256
+// product in two MFMA accumulators), reduced. Two forms of input: an element
+// per lane (made digits in place) ...
+template <class F>
+__device__ __forceinline__ Fe fold8(Fe (&x)[8], const i32x4 (&wf)[8]) {
+  i32x16 acc0, acc1;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) acc0[r] = acc1[r] = 0;
 #pragma unroll
   for (int c = 0; c < 8; ++c) {
     to_digits(x[c]);
@@ -898,19 +879,22 @@ __device__ __forceinline__ void fold_acc8(Fe (&x)[8], const i32x4* wf, i32x16& a
     acc0 = __builtin_amdgcn_mfma_i32_32x32x32_i8(wf[c], b0, acc0, 0, 0, 0);
     acc1 = __builtin_amdgcn_mfma_i32_32x32x32_i8(wf[c], b1, acc1, 0, 0, 0);
   }
+  int64_t W[8];
+  fold_words(acc0, acc1, W);
+  return dm_finish<F>(W, fe_zero<F>());
 }
-template <class F, int NP = 3>
-__device__ __forceinline__ Fe dm3_fold(Fe (&x)[1 << NP], const i32x4 (&wf)[1 << NP]) {
+// ... or whole lines (ld_half_nt): h[c] input c's elements 0-31, h[8 + c] its
+// elements 32-63, which are the B operands as they stand
+template <class F>
+__device__ __forceinline__ Fe fold8(u32x4 (&h)[16], const i32x4 (&wf)[8]) {
   i32x16 acc0, acc1;
 #pragma unroll
   for (int r = 0; r < 16; ++r) acc0[r] = acc1[r] = 0;
+  to_digits_halves<16>(h);
 #pragma unroll
-  for (int c = 0; c < (1 << NP); ++c) {
-    to_digits(x[c]);
-    i32x4 b0, b1;
-    fold_operands(x[c], b0, b1);
-    acc0 = __builtin_amdgcn_mfma_i32_32x32x32_i8(wf[c], b0, acc0, 0, 0, 0);
-    acc1 = __builtin_amdgcn_mfma_i32_32x32x32_i8(wf[c], b1, acc1, 0, 0, 0);
+  for (int c = 0; c < 8; ++c) {
+    acc0 = __builtin_amdgcn_mfma_i32_32x32x32_i8(wf[c], as_i32x4(h[c]), acc0, 0, 0, 0);
+    acc1 = __builtin_amdgcn_mfma_i32_32x32x32_i8(wf[c], as_i32x4(h[8 + c]), acc1, 0, 0, 0);
   }
   int64_t W[8];
   fold_words(acc0, acc1, W);
@@ -924,26 +908,16 @@ __global__ __launch_bounds__(kBlock, 2) void k_gkr_dm3(const Fe* __restrict__ A,
                                                       Fe* __restrict__ P2, uint64_t Q, DIn din, RoundSink sink) {
   if (blockIdx.x == 0) ZK_SINK_STAMP(sink, 0);
   __shared__ DM3Scratch sc;
-  block_get_eq8<F>(din, sc.eqw, gridDim.x > 1);  // eq((ra, rb, rc), c), c = 4a + 2b + c0
-  if (blockIdx.x == 0) ZK_SINK_STAMP(sink, 1);
   const uint32_t t = threadIdx.x, w = t >> 6, l = t & 63;
-  for (uint32_t i = t; i < kDCats * 64; i += kBlock) (&sc.T[0][0])[i] = 0;
-  __syncthreads();
-  // the constants' digit rows borrow the product image until their fragments are in registers
-  uint8_t(*wimg)[32][32] = reinterpret_cast<uint8_t(*)[32][32]>(&sc.img[0][0][0][0]);
-  dm_row<F>(wimg[t >> 5][t & 31], fe_mul<F>(sc.eqw[t >> 5], p2dig<F>(t & 31)));
-  __syncthreads();
-  i32x4 wf[8];
-#pragma unroll
-  for (int c = 0; c < 8; ++c) wf[c] = tr_frag(&wimg[c][0][0]);
-  __syncthreads();
-  const Fe* __restrict__ X = w == 0 ? A : (w == 1 ? S : (w == 2 ? M : P));
-  Fe* __restrict__ X2 = w == 0 ? A2 : (w == 1 ? S2 : (w == 2 ? M2 : P2));
+  i32x4 wf[8];  // eq((ra, rb, rc), c), c = 4a + 2b + c0
+  eq8_fragments<F>(din, sc.eqw, sc.img, wf, [&] {
+    if (blockIdx.x == 0) ZK_SINK_STAMP(sink, 1);
+    for (uint32_t i = t; i < kDCats * 64; i += kBlock) (&sc.T[0][0])[i] = 0;
+  });
+  const Fe* __restrict__ X = table_of(w, A, S, M, P);
+  Fe* __restrict__ X2 = table_of(w, A2, S2, M2, P2);
   i32x16 acc[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[i][r] = 0;
+  zero_tiles(acc);
   const uint64_t nch = Q / kDMQuads, h4 = 4 * Q;
   for (uint64_t ch = blockIdx.x; ch < nch; ch += gridDim.x) {
     const uint64_t j = ch * kDMQuads + l;
@@ -956,7 +930,7 @@ __global__ __launch_bounds__(kBlock, 2) void k_gkr_dm3(const Fe* __restrict__ A,
         ZK_DCHECK(j + k * Q + c * h4 < 8 * h4);
         x[c] = ld_fe(X, j + k * Q + c * h4);
       }
-      z[k] = dm3_fold<F>(x, wf);
+      z[k] = fold8<F>(x, wf);
       ZK_DCHECK(j + k * Q < 4 * Q);
       st_fold(X2, j + k * Q, z[k]);
     }
@@ -964,7 +938,7 @@ __global__ __launch_bounds__(kBlock, 2) void k_gkr_dm3(const Fe* __restrict__ A,
   }
   if (blockIdx.x == 0) ZK_SINK_STAMP(sink, 3);  // block 0 leaves its main loop
   ZK_BLOCK_STAMP(sink, 0);
-  dm_epilogue<F>(acc, sc, sink);
+  sum_epilogue<F>(acc, 4 * (w >> 1), sc, sink);
 }
 
 
@@ -998,201 +972,140 @@ template <int OCT>
 constexpr uint32_t kT33ChunksMax = OCT == 64 ? 128 : 256;
 static_assert((uint64_t)kT33SlotMfmas<64> * (1u << 19) * kT33ChunksMax<64> <= (1ull << 30), "t33 tile bound");
 static_assert((uint64_t)kT33SlotMfmas<32> * (1u << 19) * kT33ChunksMax<32> <= (1ull << 30), "t33 tile bound");
-struct T33Scratch {
-  uint8_t img[2][8][4][32][32];  // [buffer][corner][table][octant][digit row] (OCT 32), or [corner][table][64][32] (OCT 64)
-  unsigned long long T[kD0TCats][64];
-  uint64_t w17[kD0TCats][17];
-  uint64_t tot[kSlotU64];
-  uint64_t pp[kBlock];
-  uint32_t am_last;
-  uint32_t p2w[9][8];  // 2^(32 (8 + k)) mod p, staged at kernel start for words_to_limbs9
+// NBUF images of a chunk: two for OCT 32 and for the pipelined loop, one for
+// the plain 64-octant loop (the size of OCT 32's two)
+template <int NBUF, int OCT>
+struct T33Image {
+  uint8_t img[NBUF][8][4][OCT][32];  // [buffer][corner][table][octant][digit row]
+};
+template <int NBUF, int OCT>
+struct T33Scratch : MomentScratch<T33Image<NBUF, OCT>> {
   Fe eqw[8];
 };
 
-// PIPE (OCT 64, ZK_T33_PIPE): a double-buffered image and ONE barrier per
-// chunk; the previous chunk's 64 product MFMAs run in four groups of 16 after
-// folds 1, 3, 5 and 7 of the current chunk (while its loads are in flight)
-// instead of after a second barrier
-struct T33ScratchP {
-  uint8_t img[2][8][4][64][32];  // [buffer][corner][table][octant][digit row]
-  unsigned long long T[kD0TCats][64];
-  uint64_t w17[kD0TCats][17];
-  uint64_t tot[kSlotU64];
-  uint64_t pp[kBlock];
-  uint32_t am_last;
-  uint32_t p2w[9][8];
-  Fe eqw[8];
-};
-
-// LC (ZK_LC_LOADS, the pipelined 64-octant loop): a fold's eight inputs load
-// as whole lines with the non-temporal policy straight into the fold MFMAs' B
-// operands (ld_half_nt: elements ch 64 + u O + [0, 32) and + [32, 64) of each
-// input; to_digits_halves) instead of one element per lane (fold_operands).
-template <class F, int OCT, bool PIPE = false, bool LC = false>
-__global__ __launch_bounds__(kBlock, 1) void k_gkr_t33(const Fe* __restrict__ A, const Fe* __restrict__ S,
-                                                      const Fe* __restrict__ M, const Fe* __restrict__ P,
-                                                      Fe* __restrict__ A2, Fe* __restrict__ S2, Fe* __restrict__ M2,
-                                                      Fe* __restrict__ P2, uint64_t O, uint32_t order, DIn din,
-                                                      RoundSink sink) {
-  constexpr int NI = 8;  // inputs per output
-  if (blockIdx.x == 0) ZK_SINK_STAMP(sink, 0);
-  const uint32_t t = threadIdx.x, w = t >> 6, l = t & 63, ql = l & 31, hh = l >> 5;
-  const Fe* __restrict__ X = uniform_ptr(w == 0 ? A : (w == 1 ? S : (w == 2 ? M : P)));
-  Fe* __restrict__ X2 = w == 0 ? A2 : (w == 1 ? S2 : (w == 2 ? M2 : P2));
-  const uint64_t nch = O / OCT, h8 = 8 * O;  // level-i tables hold 8 O elements
+// Table w's side of a k_gkr_t33 block: where the lanes' inputs and outputs
+// are. Fold f of a chunk gives lane l corner f (64 / OCT) + l / OCT of the
+// chunk's octant l % OCT: for OCT 64 corner f of 64 octants, for OCT 32
+// corners 2f (lanes 0-31) and 2f + 1 (lanes 32-63) of 32. Passed by value:
+// by reference the 64-octant kernels, at the SGPR limit, spilled 3 to 11 SGPRs.
+template <int OCT>
+struct T33Io {
+  const Fe* __restrict__ X;
+  Fe* __restrict__ X2;
+  uint64_t O, nch;  // nch = O / OCT chunks; the level-i tables hold 8 O elements
+  uint32_t order;
   // order 1 (ZK_MALL_ORDER, the pass after an order-1 k_gkr_d0t): logical chunk
   // ch is physical chunk nch - 1 - ch — the chunks the previous pass read last
   // first; order 2: through t33_group_perm as the order-2 input pass
-  auto pch = [&](uint64_t ch) -> uint64_t {
+  __device__ __forceinline__ uint64_t pch(uint64_t ch) const {
     if (!order) return ch;
     return order == 2 ? t33_group_perm(nch - 1 - ch, nch) : nch - 1 - ch;
-  };
-  // A fold of a chunk past the block's last one (the prefetch two folds
-  // ahead) loads chunk 0 instead: the load stays unconditional (a conditional
-  // load made hipcc drain every load at each chunk boundary) and every block's
-  // stray loads hit the same L2-resident lines (loading the block's own chunk
-  // again reached HBM: 1.13 x the algorithmic bytes at two chunks per block).
+  }
+  // A fold of a chunk past the block's last one (the prefetch ahead) loads
+  // chunk 0 instead: the load stays unconditional (a conditional load made
+  // hipcc drain every load at each chunk boundary) and every block's stray
+  // loads hit the same L2-resident lines (loading the block's own chunk again
+  // reached HBM: 1.13 x the algorithmic bytes at two chunks per block).
   // (Measured and dropped: the same through bounds-checked buffer loads, which
   // read zeros without an access — the 8 descriptors cost the kernel 16 VGPR
   // spills and 11 SGPR spills, 512 vs 470 us for the first launch.)
-  // OCT 32: fold f = corners 2f (lanes 0-31) and 2f + 1 (lanes 32-63) of octants ch*32 + ql
-  auto in_at = [&](uint64_t ch, int f, Fe (&x)[NI]) {
-    ch = pch(ch < nch ? ch : 0);
-    const uint64_t e = ch * 32 + ql + (uint64_t)(2 * f + hh) * O;
-#pragma unroll
-    for (int k = 0; k < NI; ++k) {
-      ZK_DCHECK(e + k * h8 < 8 * h8);
-      x[k] = ld_fe(X, e + k * h8);
-    }
-  };
-  // Inputs two folds ahead for OCT 64, one for OCT 32 (one wave per SIMD: the
-  // loads in flight are what hides HBM latency). The first ones (written by
-  // the previous kernel) are in flight while the host posts the challenges.
-  // Block 0's wave 0 polls the host for the challenges and relays them to
-  // every block: its poll would wait behind these loads (vmcnt is in order),
-  // so it loads after the challenges arrive.
-  auto unit_at = [&](uint64_t ch, int u, Fe (&x)[8]) {  // OCT 64: the eight inputs of fold u (corner u of octants ch*64 + l)
-    ch = pch(ch < nch ? ch : 0);
-    const uint64_t e = ch * 64 + l + (uint64_t)u * O;
+  __device__ __forceinline__ uint64_t in_chunk(uint64_t ch) const { return pch(ch < nch ? ch : 0); }
+  // this lane's output of fold f of physical chunk pc
+  __device__ __forceinline__ uint64_t out_at(uint64_t pc, int f) const {
+    const uint32_t l = threadIdx.x & 63;
+    return pc * OCT + l % OCT + (uint64_t)(f * (64 / OCT) + l / OCT) * O;
+  }
+  // its eight inputs, an element per lane
+  __device__ __forceinline__ void load(uint64_t ch, int f, Fe (&x)[8]) const {
+    const uint64_t e = out_at(in_chunk(ch), f), h8 = 8 * O;
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       ZK_DCHECK(e + k * h8 < 8 * h8);
       x[k] = ld_fe(X, e + k * h8);
     }
-  };
-  // (LC) the halves of fold u's inputs: [k] elements ch 64 + u O + k 8 O + [0, 32), [8 + k] + [32, 64)
-  auto unit_lc = [&](uint64_t ch, int u, u32x4 (&h)[16]) {
-    ch = pch(ch < nch ? ch : 0);
-    const uint64_t e0 = ch * 64 + (uint64_t)u * O;
+  }
+  // (LC, OCT 64) the halves of fold u's inputs: [k] elements ch 64 + u O + k 8 O + [0, 32), [8 + k] + [32, 64)
+  __device__ __forceinline__ void load(uint64_t ch, int u, u32x4 (&h)[16]) const {
+    const uint64_t e0 = in_chunk(ch) * 64 + (uint64_t)u * O, h8 = 8 * O;
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       ZK_DCHECK(e0 + 63 + k * h8 < 8 * h8);
       h[k] = ld_half_nt(X, e0 + k * h8);
       h[8 + k] = ld_half_nt(X, e0 + 32 + k * h8);
     }
-  };
-  static_assert(!LC || (PIPE && OCT == 64), "lane-contiguous loads: the pipelined 64-octant loop");
-  Fe nx[8], nx2[8];
-  u32x4 ux[16], ux2[16];
-  const bool early = (uint64_t)blockIdx.x < nch && (blockIdx.x != 0 || w != 0);
-  auto first_loads = [&]() {
-    if constexpr (LC) {
-      unit_lc(blockIdx.x, 0, ux);
-      unit_lc(blockIdx.x, 1, ux2);
-    } else if constexpr (OCT == 64) {
-      unit_at(blockIdx.x, 0, nx);
-      unit_at(blockIdx.x, 1, nx2);
-    } else {
-      in_at(blockIdx.x, 0, nx);
-    }
-  };
-  if (early) first_loads();
-  static_assert(!PIPE || OCT == 64, "the pipelined loop is the 64-octant one");
-  using Scratch = std::conditional_t<PIPE, T33ScratchP, T33Scratch>;
-  __shared__ Scratch sc;
-  block_get_eq8<F>(din, sc.eqw, gridDim.x > 1);  // eq(r, c), the oldest pending challenge on c's top bit
-  if (!early && (uint64_t)blockIdx.x < nch) first_loads();
-  if (blockIdx.x == 0) ZK_SINK_STAMP(sink, 1);
-  for (uint32_t i = t; i < kD0TCats * 64; i += kBlock) (&sc.T[0][0])[i] = 0;
-  stage_p2w<F>(sc.p2w);
-  __syncthreads();
-  uint8_t(*wimg)[32][32] = reinterpret_cast<uint8_t(*)[32][32]>(&sc.img[0][0][0][0][0]);
-  for (uint32_t q = t; q < 32u * NI; q += kBlock) dm_row<F>(wimg[q >> 5][q & 31], fe_mul<F>(sc.eqw[q >> 5], p2dig<F>(q & 31)));
-  __syncthreads();
-  i32x4 wf[NI];
+  }
+  __device__ __forceinline__ void store(uint64_t ch, int f, const Fe& z) const {
+    const uint64_t e = out_at(pch(ch), f);
+    ZK_DCHECK(e < 8 * O);
+    st_fold(X2, e, z);
+  }
+};
+
+// One fold of a 64-octant chunk, two folds ahead in its loads (one wave per
+// SIMD: the loads in flight are what hides HBM latency): take fold f's inputs
+// nx, move nx2 up, load the fold two ahead into nx2 (the next chunk's first
+// two during folds 6 and 7), fold, store the output and write its digit row.
+// In = Fe[8], or u32x4[16] with whole-line loads (LC).
+template <class F, class In>
+__device__ __forceinline__ void t33_fold64(const T33Io<64> io, uint64_t ch, int f, In& nx, In& nx2,
+                                           const i32x4 (&wf)[8], uint8_t (&row)[32]) {
+  In x;
 #pragma unroll
-  for (int c = 0; c < NI; ++c) wf[c] = tr_frag(&wimg[c][0][0]);
-  __syncthreads();
-  i32x16 acc[9];
+  for (int k = 0; k < (int)std::extent_v<In>; ++k) {
+    x[k] = nx[k];
+    nx[k] = nx2[k];
+  }
+  const int u2 = f + 2;  // the fold two ahead
+  if (u2 < 8)
+    io.load(ch, u2, nx2);
+  else
+    io.load(ch + gridDim.x, u2 - 8, nx2);
+  const Fe z = fold8<F>(x, wf);
+  io.store(ch, f, z);
+  dm_row<F>(row, z);
+}
+
+// The plain 64-octant loop: eight folds into a single image, a barrier, the
+// 2 x 2 x 16 products, a barrier.
+template <class F>
+__device__ __forceinline__ void t33_loop64(const T33Io<64> io, Fe (&nx)[8], Fe (&nx2)[8], const i32x4 (&wf)[8],
+                                           T33Scratch<1, 64>& sc, i32x16 (&acc)[9]) {
+  const uint32_t w = threadIdx.x >> 6, l = threadIdx.x & 63;
+  for (uint64_t ch = blockIdx.x; ch < io.nch; ch += gridDim.x) {
 #pragma unroll
-  for (int i = 0; i < 9; ++i)
+    for (int f = 0; f < 8; ++f) t33_fold64<F>(io, ch, f, nx, nx2, wf, sc.img[0][f][w][l]);
+    __syncthreads();  // this chunk's image is complete
 #pragma unroll
-    for (int r = 0; r < 16; ++r) acc[i][r] = 0;
-  if constexpr (OCT == 64 && PIPE) {
-  uint8_t(*img2)[8][4][64][32] = reinterpret_cast<uint8_t(*)[8][4][64][32]>(&sc.img[0][0][0][0][0]);
-  const uint32_t aX = w >> 1, aY = w & 1;
+    for (int pp = 0; pp < 2; ++pp)
+#pragma unroll
+      for (int half = 0; half < 2; ++half)  // K = the 64 octants in two MFMA steps
+        moment_products(sc.img[0], 2 * pp, 2 * pp + 1, 32 * half, acc);
+    __syncthreads();  // the image is rewritten by the next chunk
+  }
+}
+
+// PIPE (OCT 64, ZK_T33_PIPE): a double-buffered image and ONE barrier per
+// chunk; the previous chunk's 64 product MFMAs run in four groups of 16 after
+// folds 1, 3, 5 and 7 of the current chunk (while its loads are in flight)
+// instead of after a second barrier.
+// LC (ZK_LC_LOADS, In = u32x4[16]): a fold's eight inputs load as whole lines
+// with the non-temporal policy straight into the fold MFMAs' B operands
+// (ld_half_nt: elements ch 64 + u O + [0, 32) and + [32, 64) of each input;
+// to_digits_halves) instead of one element per lane (fold_operands).
+template <class F, class In>
+__device__ __forceinline__ void t33_loop64_pipe(const T33Io<64> io, In& nx, In& nx2, const i32x4 (&wf)[8],
+                                                T33Scratch<2, 64>& sc, i32x16 (&acc)[9]) {
+  const uint32_t w = threadIdx.x >> 6, l = threadIdx.x & 63;
   auto products = [&](uint32_t b, int grp) {  // group grp = (pp, K half) of a chunk's products from image b
     const int pp = grp >> 1, half = grp & 1;
-    i32x4 fa[4], fb[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      fa[k] = tr_frag(&img2[b][4 * aX + k][2 * pp][32 * half][0]);
-      fb[k] = tr_frag(&img2[b][4 * aY + k][2 * pp + 1][32 * half][0]);
-    }
-#pragma unroll
-    for (int ux = 0; ux < 4; ++ux)
-#pragma unroll
-      for (int vy = 0; vy < 4; ++vy) {
-        const int slot = 3 * moment_digit(ux >> 1, vy >> 1) + moment_digit(ux & 1, vy & 1);
-        acc[slot] = __builtin_amdgcn_mfma_i32_32x32x32_i8(fa[ux], fb[vy], acc[slot], 0, 0, 0);
-      }
+    moment_products(sc.img[b], 2 * pp, 2 * pp + 1, 32 * half, acc);
   };
   uint32_t buf = 0;
   bool prev = false;
-  for (uint64_t ch = blockIdx.x; ch < nch; ch += gridDim.x, buf ^= 1) {
+  for (uint64_t ch = blockIdx.x; ch < io.nch; ch += gridDim.x, buf ^= 1) {
 #pragma unroll
     for (int f = 0; f < 8; ++f) {
-      i32x16 a0, a1;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) a0[r] = a1[r] = 0;
-      if constexpr (LC) {
-        u32x4 x[16];
-#pragma unroll
-        for (int k = 0; k < 16; ++k) {
-          x[k] = ux[k];
-          ux[k] = ux2[k];
-        }
-        const int u2 = f + 2;  // the fold two ahead
-        if (u2 < 8)
-          unit_lc(ch, u2, ux2);
-        else
-          unit_lc(ch + gridDim.x, u2 - 8, ux2);
-        to_digits_halves<16>(x);
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-          a0 = __builtin_amdgcn_mfma_i32_32x32x32_i8(wf[c], as_i32x4(x[c]), a0, 0, 0, 0);
-          a1 = __builtin_amdgcn_mfma_i32_32x32x32_i8(wf[c], as_i32x4(x[8 + c]), a1, 0, 0, 0);
-        }
-      } else {
-        Fe x[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-          x[k] = nx[k];
-          nx[k] = nx2[k];
-        }
-        const int u2 = f + 2;  // the fold two ahead
-        if (u2 < 8)
-          unit_at(ch, u2, nx2);
-        else
-          unit_at(ch + gridDim.x, u2 - 8, nx2);
-        fold_acc8(x, wf, a0, a1);
-      }
-      int64_t W[8];
-      fold_words(a0, a1, W);
-      const Fe z = dm_finish<F>(W, fe_zero<F>());
-      ZK_DCHECK(pch(ch) * 64 + l + (uint64_t)f * O < 8 * O);
-      st_fold(X2, pch(ch) * 64 + l + (uint64_t)f * O, z);
-      dm_row<F>(img2[buf][f][w][l], z);
+      t33_fold64<F>(io, ch, f, nx, nx2, wf, sc.img[buf][f][w][l]);
       if ((f & 1) && prev) products(buf ^ 1, f >> 1);  // the previous chunk's products, a quarter at a time
     }
     __syncthreads();  // this chunk's image is complete; the previous one's products are done (its buffer is free)
@@ -1201,107 +1114,80 @@ __global__ __launch_bounds__(kBlock, 1) void k_gkr_t33(const Fe* __restrict__ A,
   if (prev)
 #pragma unroll
     for (int grp = 0; grp < 4; ++grp) products(buf ^ 1, grp);  // the last chunk's products
-  } else if constexpr (OCT == 64) {
-  uint8_t(*img)[4][64][32] = reinterpret_cast<uint8_t(*)[4][64][32]>(&sc.img[0][0][0][0][0]);
-  for (uint64_t ch = blockIdx.x; ch < nch; ch += gridDim.x) {
-#pragma unroll
-    for (int f = 0; f < 8; ++f) {
-      i32x16 a0, a1;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) a0[r] = a1[r] = 0;
-      {
-        Fe x[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-          x[k] = nx[k];
-          nx[k] = nx2[k];
-        }
-        const int u2 = f + 2;  // the fold two ahead
-        if (u2 < 8)
-          unit_at(ch, u2, nx2);
-        else
-          unit_at(ch + gridDim.x, u2 - 8, nx2);
-        fold_acc8(x, wf, a0, a1);
-      }
-      int64_t W[8];
-      fold_words(a0, a1, W);
-      const Fe z = dm_finish<F>(W, fe_zero<F>());
-      ZK_DCHECK(pch(ch) * 64 + l + (uint64_t)f * O < 8 * O);
-      st_fold(X2, pch(ch) * 64 + l + (uint64_t)f * O, z);
-      dm_row<F>(img[f][w][l], z);
-    }
-    __syncthreads();  // this chunk's image is complete
-    const uint32_t aX = w >> 1, aY = w & 1;
-#pragma unroll
-    for (int pp = 0; pp < 2; ++pp)
-#pragma unroll
-      for (int half = 0; half < 2; ++half) {  // K = the 64 octants in two MFMA steps
-        i32x4 fa[4], fb[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          fa[k] = tr_frag(&img[4 * aX + k][2 * pp][32 * half][0]);
-          fb[k] = tr_frag(&img[4 * aY + k][2 * pp + 1][32 * half][0]);
-        }
-#pragma unroll
-        for (int ux = 0; ux < 4; ++ux)
-#pragma unroll
-          for (int vy = 0; vy < 4; ++vy) {
-            const int slot = 3 * moment_digit(ux >> 1, vy >> 1) + moment_digit(ux & 1, vy & 1);
-            acc[slot] = __builtin_amdgcn_mfma_i32_32x32x32_i8(fa[ux], fb[vy], acc[slot], 0, 0, 0);
-          }
-      }
-    __syncthreads();  // the image is rewritten by the next chunk
-  }
-  } else {
-  // (OCT 32: one fold ahead and a rolled fold loop — the small levels are
-  // latency-bound, and the unrolled loop with two folds in flight spilled 55
-  // VGPRs, whose scratch traffic was 0.4 x the kernel's bytes)
+}
+
+// The 32-octant loop: one fold ahead and a rolled fold loop — the small levels
+// are latency-bound, and the unrolled loop with two folds in flight spilled 55
+// VGPRs, whose scratch traffic was 0.4 x the kernel's bytes. One barrier per
+// chunk (double buffering).
+template <class F>
+__device__ __forceinline__ void t33_loop32(const T33Io<32> io, Fe (&nx)[8], const i32x4 (&wf)[8],
+                                           T33Scratch<2, 32>& sc, i32x16 (&acc)[9]) {
+  const uint32_t w = threadIdx.x >> 6, l = threadIdx.x & 63;
   uint32_t buf = 0;
-  for (uint64_t ch = blockIdx.x; ch < nch; ch += gridDim.x, buf ^= 1) {
+  for (uint64_t ch = blockIdx.x; ch < io.nch; ch += gridDim.x, buf ^= 1) {
 #pragma unroll 1
     for (int f = 0; f < 4; ++f) {
       Fe x[8];
 #pragma unroll
       for (int k = 0; k < 8; ++k) x[k] = nx[k];
       // the next fold (one load site, no branch; past the end: chunk 0, L2-resident)
-      in_at(f < 3 ? ch : ch + gridDim.x, f < 3 ? f + 1 : 0, nx);
-      const uint32_t corner = 2 * f + hh;
-      const Fe z = dm3_fold<F>(x, wf);
-      ZK_DCHECK(pch(ch) * 32 + ql + (uint64_t)corner * O < 8 * O);
-      st_fold(X2, pch(ch) * 32 + ql + (uint64_t)corner * O, z);
-      dm_row<F>(sc.img[buf][corner][w][ql], z);
+      io.load(f < 3 ? ch : ch + gridDim.x, f < 3 ? f + 1 : 0, nx);
+      const Fe z = fold8<F>(x, wf);
+      io.store(ch, f, z);
+      dm_row<F>(sc.img[buf][2 * f + (l >> 5)][w][l & 31], z);
     }
     __syncthreads();  // this chunk's image is complete (double buffering: one barrier per chunk)
-    const uint32_t aX = w >> 1, aY = w & 1;
 #pragma unroll
-    for (int pp = 0; pp < 2; ++pp) {
-      i32x4 fa[4], fb[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        fa[k] = tr_frag(&sc.img[buf][4 * aX + k][2 * pp][0][0]);
-        fb[k] = tr_frag(&sc.img[buf][4 * aY + k][2 * pp + 1][0][0]);
-      }
-#pragma unroll
-      for (int ux = 0; ux < 4; ++ux)
-#pragma unroll
-        for (int vy = 0; vy < 4; ++vy) {
-          const int slot = 3 * moment_digit(ux >> 1, vy >> 1) + moment_digit(ux & 1, vy & 1);
-          acc[slot] = __builtin_amdgcn_mfma_i32_32x32x32_i8(fa[ux], fb[vy], acc[slot], 0, 0, 0);
-        }
-    }
+    for (int pp = 0; pp < 2; ++pp) moment_products(sc.img[buf], 2 * pp, 2 * pp + 1, 0, acc);
   }
-  }
+}
+
+template <class F, int OCT, bool PIPE = false, bool LC = false>
+__global__ __launch_bounds__(kBlock, 1) void k_gkr_t33(const Fe* __restrict__ A, const Fe* __restrict__ S,
+                                                      const Fe* __restrict__ M, const Fe* __restrict__ P,
+                                                      Fe* __restrict__ A2, Fe* __restrict__ S2, Fe* __restrict__ M2,
+                                                      Fe* __restrict__ P2, uint64_t O, uint32_t order, DIn din,
+                                                      RoundSink sink) {
+  static_assert(!PIPE || OCT == 64, "the pipelined loop is the 64-octant one");
+  static_assert(!LC || PIPE, "lane-contiguous loads: the pipelined 64-octant loop");
+  if (blockIdx.x == 0) ZK_SINK_STAMP(sink, 0);
+  const uint32_t t = threadIdx.x, w = t >> 6;
+  const T33Io<OCT> io{uniform_ptr(table_of(w, A, S, M, P)), table_of(w, A2, S2, M2, P2), O, O / OCT, order};
+  // Inputs two folds ahead for OCT 64, one for OCT 32 (one wave per SIMD: the
+  // loads in flight are what hides HBM latency). The first ones (written by
+  // the previous kernel) are in flight while the host posts the challenges.
+  // Block 0's wave 0 polls the host for the challenges and relays them to
+  // every block: its poll would wait behind these loads (vmcnt is in order),
+  // so it loads after the challenges arrive.
+  using In = std::conditional_t<LC, u32x4[16], Fe[8]>;
+  In nx, nx2;
+  const bool early = (uint64_t)blockIdx.x < io.nch && (blockIdx.x != 0 || w != 0);
+  auto first_loads = [&]() {
+    io.load(blockIdx.x, 0, nx);
+    if constexpr (OCT == 64) io.load(blockIdx.x, 1, nx2);
+  };
+  if (early) first_loads();
+  __shared__ T33Scratch<PIPE || OCT == 32 ? 2 : 1, OCT> sc;
+  i32x4 wf[8];
+  eq8_fragments<F>(din, sc.eqw, sc.img, wf, [&] {
+    if (!early && (uint64_t)blockIdx.x < io.nch) first_loads();
+    if (blockIdx.x == 0) ZK_SINK_STAMP(sink, 1);
+    for (uint32_t i = t; i < kD0TCats * 64; i += kBlock) (&sc.T[0][0])[i] = 0;
+    stage_p2w<F>(sc.p2w);
+  });
+  i32x16 acc[9];
+  zero_tiles(acc);
+  if constexpr (PIPE)
+    t33_loop64_pipe<F>(io, nx, nx2, wf, sc, acc);
+  else if constexpr (OCT == 64)
+    t33_loop64<F>(io, nx, nx2, wf, sc, acc);
+  else
+    t33_loop32<F>(io, nx, wf, sc, acc);
   if (blockIdx.x == 0) ZK_SINK_STAMP(sink, 3);  // block 0 leaves its main loop
   ZK_BLOCK_STAMP(sink, 0);
-  __syncthreads();
-  d0t_flush(acc, sc.T);
-  __syncthreads();
-  ZK_BLOCK_STAMP(sink, 4);
-  tiles_to_words<F, kD0TCats>(sc.T, sc.w17);
-  ZK_BLOCK_STAMP(sink, 5);
-  words_to_limbs9<F, kD0TCats>(sc.w17, sc.p2w, sc.tot);
-  __syncthreads();
-  grid_finish<kD0TLimbs>(sc, sink);
+  moment_epilogue<F, true>(acc, sc, sink);
 }
 
 }  // namespace zk
+

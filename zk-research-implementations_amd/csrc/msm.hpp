@@ -21,8 +21,6 @@ namespace zk {
 constexpr uint32_t kSegTask = 32;    // points summed by one thread per reduction level
 constexpr uint32_t kBucketChunkMax = 32;  // buckets per thread in the window reduction (host-chosen, a power of two <= 32: c >= 6)
 
-__device__ __forceinline__ Fq ld_fq(const Fq* p, uint64_t i) { return p[i]; }
-
 // ---- exclusive scan of u32 (in place), 2048 per block ------------------------
 constexpr uint32_t kScanPer = 8, kScanBlock = kBlock * kScanPer;
 __global__ __launch_bounds__(kBlock) void k_scan_block(uint32_t* __restrict__ a, uint64_t n,

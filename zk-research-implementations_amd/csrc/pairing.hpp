@@ -114,20 +114,6 @@ inline Fq12 fq12_inv(const Fq12& a) {  // (c0 - c1 w) / (c0^2 - v c1^2)
   const Fq6 t = fq6_inv(fq6_sub(fq6_mul(a.c0, a.c0), fq6_mul_v(fq6_mul(a.c1, a.c1))));
   return {fq6_mul(a.c0, t), fq6_neg(fq6_mul(a.c1, t))};
 }
-// a^e, e as little-endian u32 limbs (MSB-first square and multiply)
-inline Fq12 fq12_pow(const Fq12& a, const std::vector<uint32_t>& e) {
-  Fq12 r = fq12_one();
-  bool started = false;
-  for (size_t i = e.size(); i-- > 0;)
-    for (int b = 31; b >= 0; --b) {
-      if (started) r = fq12_sqr(r);
-      if ((e[i] >> b) & 1u) {
-        r = started ? fq12_mul(r, a) : a;
-        started = true;
-      }
-    }
-  return r;
-}
 
 // ---- small unsigned big integers (u32 limbs, LE) for the exponent -------------
 namespace bigu {
