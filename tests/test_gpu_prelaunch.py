@@ -173,6 +173,29 @@ def test_dtail_modes_agree(monkeypatch, field, env, n):
         ctx.close()
 
 
+@pytest.mark.parametrize("field", [0, 1, 2])
+@pytest.mark.parametrize("env", [{}, {"ZK_DROUND": "0", "ZK_TAIL": "0"}], ids=["default", "single-rounds"])
+def test_slot_tree_fan_in_matches_oracle(monkeypatch, field, env):
+    """ZK_ATOMIC_FANIN=1 sends every multi-block grid through the two-level
+    slot tree of grid_finish (per-block slots, blockIdx % 8 shards, a top
+    counter), which the default 1024 keeps for grids no test launches. n = 12
+    is the smallest size whose first rounds span more than eight blocks of
+    256 threads: the shrinking grids pass through 16, 8, 4 and 2 blocks (more
+    than eight shards' worth, exactly eight, fewer than eight), with the
+    default schedule and with the single rounds launched one by one."""
+    n = 12
+    want = _oracle(field, n)
+    monkeypatch.setenv("ZK_ATOMIC_FANIN", "1")
+    for key, val in env.items():
+        monkeypatch.setenv(key, val)
+    ctx = zk_amd.Context(0)
+    try:
+        assert _prove(ctx, field, n) == want
+        assert _prove(ctx, field, n) == want  # the shard and top counters were re-armed
+    finally:
+        ctx.close()
+
+
 def test_host_failure_mid_proof_releases_waiting_rounds(monkeypatch):
     monkeypatch.setenv("ZK_FORCE_COLLECTIVES", "1")  # route every round through the host all-reduce at world 1
     ctx = zk_amd.Context(0)

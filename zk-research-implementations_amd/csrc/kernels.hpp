@@ -55,29 +55,55 @@ __device__ __forceinline__ void st_fe(Fe* __restrict__ p, uint64_t i, const Fe& 
   q[0] = make_uint4(x.v[0], x.v[1], x.v[2], x.v[3]);
   q[1] = make_uint4(x.v[4], x.v[5], x.v[6], x.v[7]);
 }
-
-// Folded-table stores. ZK_FOLD_STORE: 0 plain (write-back L2), 1 non-temporal
-// hint, 2 write-through (sc1) so the kernel does not end with the L2 full of
-// dirty table lines to write back.
-#ifndef ZK_FOLD_STORE
-#define ZK_FOLD_STORE 0
-#endif
+// (Folded tables are stored with st_fe too: plain write-back stores. A
+// non-temporal hint and write-through (sc1) stores were tried, so that a round
+// would not end with the L2 full of dirty table lines; plain stores won.)
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void st_fold(Fe* __restrict__ p, uint64_t i, const Fe& x) {
-#if ZK_FOLD_STORE == 0
-  st_fe(p, i, x);
-#else
-  u32x4* q = reinterpret_cast<u32x4*>(p) + 2 * i;
-  const u32x4 a = {x.v[0], x.v[1], x.v[2], x.v[3]}, b = {x.v[4], x.v[5], x.v[6], x.v[7]};
-#if ZK_FOLD_STORE == 1
-  __builtin_nontemporal_store(a, q);
-  __builtin_nontemporal_store(b, q + 1);
-#else
-  asm volatile("global_store_dwordx4 %0, %1, off sc1\n\tglobal_store_dwordx4 %0, %2, off offset:16 sc1"
-               :: "v"(q), "v"(a), "v"(b) : "memory");
-#endif
-#endif
+
+// An element as four 64-bit words (the 8-byte accesses of the tables that
+// blocks hand to each other, and of the host tables): word k = limbs 2k, 2k+1.
+__device__ __forceinline__ uint64_t fe_word64(const Fe& x, int k) {
+  return (uint64_t)x.v[2 * k] | ((uint64_t)x.v[2 * k + 1] << 32);
 }
+__device__ __forceinline__ void fe_set_word64(Fe& x, int k, uint64_t w) {
+  x.v[2 * k] = (uint32_t)w;
+  x.v[2 * k + 1] = (uint32_t)(w >> 32);
+}
+// Element loads and stores whose bytes another block of the SAME kernel reads
+// or wrote (k_gkr_tail, k_gkr_dtail): relaxed agent-scope 8-byte atomics (sc1)
+// on both sides, MI355X_MICROARCH.md "Valid forms".
+__device__ __forceinline__ Fe ld_fe_a(const Fe* p, uint64_t i) {
+  const uint64_t* q = reinterpret_cast<const uint64_t*>(p + i);
+  Fe r;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) fe_set_word64(r, k, __hip_atomic_load(q + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+  return r;
+}
+__device__ __forceinline__ void st_fe_a(Fe* p, uint64_t i, const Fe& x) {
+  uint64_t* q = reinterpret_cast<uint64_t*>(p + i);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) __hip_atomic_store(q + k, fe_word64(x, k), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// element i of a word-major table of n elements in pinned host memory (word k
+// at k n + i), system-scope stores: see k_gkr_dtail
+__device__ __forceinline__ void st_fe_sys(uint64_t* p, uint64_t n, uint64_t i, const Fe& x) {
+#pragma unroll
+  for (int k = 0; k < 4; ++k) __hip_atomic_store(p + k * n + i, fe_word64(x, k), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+// How a round step reads and writes table elements: a one-launch kernel with
+// plain 32-byte accesses, all loads of an output issued before any arithmetic
+// where the step says so (sched_barrier, the tuned form of the double round);
+// a persistent kernel with the agent-scope atomics above and no such fence.
+struct PlainIo {
+  static __device__ __forceinline__ Fe ld(const Fe* p, uint64_t i) { return ld_fe(p, i); }
+  static __device__ __forceinline__ void st(Fe* p, uint64_t i, const Fe& x) { st_fe(p, i, x); }
+  static __device__ __forceinline__ void loads_first() { __builtin_amdgcn_sched_barrier(0); }
+};
+struct AgentIo {
+  static __device__ __forceinline__ Fe ld(const Fe* p, uint64_t i) { return ld_fe_a(p, i); }
+  static __device__ __forceinline__ void st(Fe* p, uint64_t i, const Fe& x) { st_fe_a(p, i, x); }
+  static __device__ __forceinline__ void loads_first() {}
+};
 
 // a + r (b - a)
 template <class F>
@@ -312,61 +338,59 @@ struct alignas(64) RWait {
 struct RoundIn {
   Fe r;                // used as is when host == null
   const RWait* host;   // pinned slot the host posts r to, or null
-  RWait* relay;        // kRelays device relay slots (zeroed tags at rest), used when gridDim > 1
+  RWait* relay;        // device relay slot (zeroed tag at rest), used when gridDim > 1
   uint32_t* err;       // pinned error word
   uint32_t tag;
 };
 constexpr uint64_t kWaitTicks = 100000000ull;  // 1 s of s_memrealtime (100 MHz)
-#ifndef ZK_RELAYS
-#define ZK_RELAYS 1
-#endif
-#ifndef ZK_RELAY_SLEEP
-#define ZK_RELAY_SLEEP 1
-#endif
-constexpr uint32_t kRelays = ZK_RELAYS;  // block b polls relay b % kRelays (1 measured best: 8 replicas cost block 0 more than they save)
 
-__device__ __forceinline__ Fe block_get_r(const RoundIn& in) {
-  if (!in.host) return in.r;
+// The challenge the host posts to `host` under `tag`, in every thread of the
+// block (ends with a barrier). Thread 0 of block 0 polls the host slot and,
+// when other blocks wait too (`relayed`), copies r to the one relay slot:
+// write-through stores, drained before the tag that announces them. Thread 0
+// of every other block polls the relay (sleep 1 between polls). One slot that
+// all blocks poll measured best: 8 replicas (block b polling slot b % 8) cost
+// block 0 more than they saved the pollers. A wait that runs out sets *err.
+__device__ __forceinline__ Fe block_wait_r(const RWait* host, RWait* relay, bool relayed, uint32_t tag, uint32_t* err) {
   __shared__ Fe s_r;
   if (threadIdx.x == 0) {
-    const bool direct = blockIdx.x == 0;
     const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
     bool ok = true;
     Fe r;
-    if (direct) {
+    if (blockIdx.x == 0) {
       // relaxed system-scope polls: uncached (sc0 sc1) loads with no cache
       // invalidate per iteration; the r loads below are uncached too and issue
       // only after the tag has been seen
-      while ((int32_t)(__hip_atomic_load(&in.host->tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) - in.tag) < 0) {
+      while ((int32_t)(__hip_atomic_load(&host->tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) - tag) < 0) {
         __builtin_amdgcn_s_sleep(2);
         if (__builtin_amdgcn_s_memrealtime() - t0 > kWaitTicks) { ok = false; break; }
       }
 #pragma unroll
-      for (int i = 0; i < 8; ++i) r.v[i] = __hip_atomic_load(&in.host->r.v[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      if (gridDim.x > 1) {  // block 0 relays (write-through stores, drained before the tags)
-        const uint32_t nrel = gridDim.x < kRelays ? gridDim.x : kRelays;
-        for (uint32_t k = 0; k < nrel; ++k)
+      for (int i = 0; i < 8; ++i) r.v[i] = __hip_atomic_load(&host->r.v[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      if (relayed) {
 #pragma unroll
-          for (int i = 0; i < 8; ++i)
-            __hip_atomic_store(&in.relay[k].r.v[i], r.v[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        for (int i = 0; i < 8; ++i) __hip_atomic_store(&relay->r.v[i], r.v[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        for (uint32_t k = 0; k < nrel; ++k)
-          __hip_atomic_store(&in.relay[k].tag, in.tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&relay->tag, tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
     } else {
-      const RWait* rl = in.relay + blockIdx.x % kRelays;
-      while ((int32_t)(__hip_atomic_load(&rl->tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - in.tag) < 0) {
-        __builtin_amdgcn_s_sleep(ZK_RELAY_SLEEP);
+      while ((int32_t)(__hip_atomic_load(&relay->tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - tag) < 0) {
+        __builtin_amdgcn_s_sleep(1);
         if (__builtin_amdgcn_s_memrealtime() - t0 > kWaitTicks) { ok = false; break; }
       }
 #pragma unroll
-      for (int i = 0; i < 8; ++i) r.v[i] = __hip_atomic_load(&rl->r.v[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      for (int i = 0; i < 8; ++i) r.v[i] = __hip_atomic_load(&relay->r.v[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    if (!ok) __hip_atomic_store(in.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    if (!ok) __hip_atomic_store(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     s_r = r;
   }
   __syncthreads();
   return s_r;
+}
+// a round kernel's challenge: the argument itself, or awaited (pre-enqueued rounds)
+__device__ __forceinline__ Fe block_get_r(const RoundIn& in) {
+  if (!in.host) return in.r;
+  return block_wait_r(in.host, in.relay, gridDim.x > 1, in.tag, in.err);
 }
 
 __device__ __forceinline__ void st_u64_sc1(uint64_t* p, uint64_t v) {
@@ -513,6 +537,46 @@ __device__ __forceinline__ void sum_slots(uint64_t* slots, uint32_t first, uint3
   }
 }
 
+// Counting in: what a block wrote for the others (slot stores, accumulator
+// adds, table stores) is complete before the others can see it counted. Every
+// wave drains its own stores (vmcnt(0)), the barrier collects the waves, then
+// thread 0 adds 1 to `counter` (and first zeroes `rearm`, a counter this block
+// was the last to count in on, for the next launch). True in every thread of
+// the n-th block to arrive (after a second barrier); what that block then
+// reads are device-coherent accesses (sc1 / atomics) that hit the values
+// drained before the adds. The acquire fence at wavefront scope emits no
+// instruction: it keeps the compiler from moving those reads above the add.
+template <class Sc>
+__device__ __forceinline__ bool count_in(Sc& sc, uint32_t* counter, uint32_t n, uint32_t* rearm = nullptr) {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    if (rearm) __hip_atomic_store(rearm, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const uint32_t prev = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    sc.am_last = prev == n - 1;
+  }
+  __syncthreads();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  return sc.am_last;
+}
+
+// Fan-in of n blocks through the u64 accumulator: every block adds its limb
+// sums sc.tot[0..C) (no-return u64 atomics, device-coherent level; n * 256 *
+// 2^32 < 2^64 stays exact) and counts in; the last one takes the totals back
+// into sc.tot (threads < C) and re-arms accumulator and counter for the next
+// use. Returns whether this block is that last one.
+template <int C, class Sc>
+__device__ __forceinline__ bool atomic_fan_in(Sc& sc, const RoundSink& sk, uint32_t n) {
+  const uint32_t t = threadIdx.x;
+  if (t < (uint32_t)C) __hip_atomic_fetch_add(sk.accum + t, sc.tot[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const bool last = count_in(sc, sk.counter, n);
+  if (last) {
+    if (t < (uint32_t)C)
+      sc.tot[t] = __hip_atomic_exchange(sk.accum + t, (uint64_t)0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (t == 0) __hip_atomic_store(sk.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  return last;
+}
 
 // Block limb sums are in sc.tot[0..C) (valid for threads < C); finish over the grid.
 // G: the blocks taking part (blocks 0 .. G-1; default the whole grid).
@@ -530,23 +594,10 @@ __device__ __forceinline__ void grid_finish(Sc& sc, const RoundSink& sk, uint32_
     return;
   }
   if (G <= sk.atomic_max) {
-    // every block adds its limb sums (no-return u64 atomics, device-coherent
-    // level; G * 256 * 2^32 < 2^64 stays exact), drains, and counts in
-    if (t < (uint32_t)C) __hip_atomic_fetch_add(sk.accum + t, sc.tot[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (t == 0) {
-      const uint32_t prev = __hip_atomic_fetch_add(sk.counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      sc.am_last = prev == G - 1;
-    }
-    __syncthreads();
+    const bool last = atomic_fan_in<C>(sc, sk, G);
     ZK_STAMP(4);
     ZK_BLOCK_STAMP(sk, 2);
-    if (!sc.am_last) return;
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    if (t < (uint32_t)C)  // read and re-arm for the next launch
-      sc.tot[t] = __hip_atomic_exchange(sk.accum + t, (uint64_t)0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (t == 0) __hip_atomic_store(sk.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (!last) return;
     ZK_STAMP(5);
     publish_limbs<C>(sc, sk);
     ZK_STAMP(6);
@@ -555,30 +606,13 @@ __device__ __forceinline__ void grid_finish(Sc& sc, const RoundSink& sk, uint32_
   const uint32_t shard = blockIdx.x & 7u, nshards = G < 8 ? G : 8u;
   const uint32_t in_shard = (G - shard + 7u) / 8u;
   if (t < (uint32_t)C) st_u64_sc1(sk.partials + (uint64_t)blockIdx.x * kSlotU64 + t, sc.tot[t]);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the storing wave drains before the signal
-  __syncthreads();
-  if (t == 0) {
-    const uint32_t prev =
-        __hip_atomic_fetch_add(sk.counter + 32 * shard, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    sc.am_last = prev == in_shard - 1;
-  }
-  __syncthreads();
+  const bool last_in_shard = count_in(sc, sk.counter + 32 * shard, in_shard);
   ZK_STAMP(4);
   ZK_BLOCK_STAMP(sk, 2);
-  if (!sc.am_last) return;
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");  // no instruction: keeps the loads below the add
+  if (!last_in_shard) return;
   sum_slots<C>(sk.partials, shard, 8u, in_shard, sc);
   if (t < (uint32_t)C) st_u64_sc1(sk.partials + (uint64_t)(G + shard) * kSlotU64 + t, sc.tot[t]);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (t == 0) {
-    __hip_atomic_store(sk.counter + 32 * shard, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // next launch
-    const uint32_t prev = __hip_atomic_fetch_add(sk.counter + 32 * 8, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    sc.am_last = prev == nshards - 1;
-  }
-  __syncthreads();
-  if (!sc.am_last) return;
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  if (!count_in(sc, sk.counter + 32 * 8, nshards, /*rearm=*/sk.counter + 32 * shard)) return;
   __syncthreads();  // pp is reused
   sum_slots<C>(sk.partials, G, 1u, nshards, sc);
   if (t == 0) __hip_atomic_store(sk.counter + 32 * 8, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -651,19 +685,12 @@ __global__ __launch_bounds__(kBlock) void k_gkr_round0(const Fe* __restrict__ A,
 // derives it exactly as s_{k-1}(r_{k-1}) - e0. out must not alias
 // in (the host ping-pongs two workspaces). 8 reduced muls + 4 unreduced products / pair.
 // ---------------------------------------------------------------------------
-// A/B knobs (defaults are the tuned values): minimum waves per SIMD for the
-// fused round kernel, and whether all loads are forced ahead of the arithmetic.
-#ifndef ZK_ROUND_WAVES
-#define ZK_ROUND_WAVES 1
-#endif
-#ifndef ZK_ROUND_FOLDC  // round 1 folds with the per-block constant tables (1) or fe_mul (0)
-#define ZK_ROUND_FOLDC 1
-#endif
-#ifndef ZK_ROUND_LOADS_FIRST
-#define ZK_ROUND_LOADS_FIRST 1
-#endif
+// Measured choices: one wave per SIMD with all 256 VGPRs (asking for two made
+// the kernel spill and run slower); all eight loads issued ahead of the
+// arithmetic; the folds by the step-constant tables (fold1c) rather than
+// fe_mul.
 template <class F>
-__global__ __launch_bounds__(kBlock, ZK_ROUND_WAVES) void k_gkr_round(const Fe* __restrict__ A, const Fe* __restrict__ S,
+__global__ __launch_bounds__(kBlock, 1) void k_gkr_round(const Fe* __restrict__ A, const Fe* __restrict__ S,
                                                       const Fe* __restrict__ M, const Fe* __restrict__ P,
                                                       Fe* __restrict__ A2, Fe* __restrict__ S2,
                                                       Fe* __restrict__ M2, Fe* __restrict__ P2, uint64_t h,
@@ -672,10 +699,8 @@ __global__ __launch_bounds__(kBlock, ZK_ROUND_WAVES) void k_gkr_round(const Fe* 
   if (blockIdx.x == 0) ZK_SINK_STAMP(sink, 0);
   const Fe r = block_get_r(rin);
   if (blockIdx.x == 0) ZK_SINK_STAMP(sink, 1);
-#if ZK_ROUND_FOLDC
   __shared__ Fe ct[10];
   fold_consts<F, 1>(r, r, r, ct);
-#endif
   Wide w0 = wide_zero<F>(), w2 = wide_zero<F>();
   uint64_t j, step;
   uint32_t q;
@@ -687,20 +712,13 @@ __global__ __launch_bounds__(kBlock, ZK_ROUND_WAVES) void k_gkr_round(const Fe* 
   for (; j < h; j += step) {
     const Fe x0 = ld_fe(X, j), x1 = ld_fe(X, j + h), x2 = ld_fe(X, j + 2 * h), x3 = ld_fe(X, j + 3 * h);
     const Fe z0 = ld_fe(Z, j), z1 = ld_fe(Z, j + h), z2 = ld_fe(Z, j + 2 * h), z3 = ld_fe(Z, j + 3 * h);
-#if ZK_ROUND_LOADS_FIRST
     __builtin_amdgcn_sched_barrier(0);  // issue all loads before any arithmetic
-#endif
-#if ZK_ROUND_FOLDC
     const Fe a0 = fold1c<F, 0>(x0, x2, ct), a1 = fold1c<F, 0>(x1, x3, ct);
     const Fe s0 = fold1c<F, 0>(z0, z2, ct), s1 = fold1c<F, 0>(z1, z3, ct);
-#else
-    const Fe a0 = fold1<F>(x0, x2, r), a1 = fold1<F>(x1, x3, r);
-    const Fe s0 = fold1<F>(z0, z2, r), s1 = fold1<F>(z1, z3, r);
-#endif
-    st_fold(X2, j, a0);
-    st_fold(X2, j + h, a1);
-    st_fold(Z2, j, s0);
-    st_fold(Z2, j + h, s1);
+    st_fe(X2, j, a0);
+    st_fe(X2, j + h, a1);
+    st_fe(Z2, j, s0);
+    st_fe(Z2, j + h, s1);
     wide_mac<F>(w0, a0, s0);
     wide_mac<F>(w2, at2<F>(a0, a1), at2<F>(s0, s1));
   }
@@ -728,6 +746,39 @@ __device__ __forceinline__ Fe shfl_fe(const Fe& x, int src) {
   for (int i = 0; i < 8; ++i) r.v[i] = __shfl(x.v[i], src, 64);
   return r;
 }
+// The step over h pairs by nb blocks: this lane's table X (4h elements, table
+// (threadIdx & 7) >> 1 of A, S, M, P) folds by r into Y (2h). Returns the
+// lane's unreduced product sum: lanes 0,4 of a group the t = 0 products,
+// lanes 1,5 the t = 2 products, the others unused.
+template <class F, class Io>
+__device__ __forceinline__ Wide lanes_pairs(const Fe* __restrict__ X, Fe* __restrict__ Y, uint64_t h, const Fe& r,
+                                            uint32_t nb) {
+  const uint32_t lane = threadIdx.x & 63, half = threadIdx.x & 1;
+  Wide acc = wide_zero<F>();
+  const uint64_t stride = (uint64_t)nb * (kBlock / 8);
+  // the loop bound is uniform per 8-lane group (and per wave: 8 groups share j's stride)
+  for (uint64_t j = ((uint64_t)blockIdx.x * kBlock + threadIdx.x) >> 3; j < h; j += stride) {
+    const uint64_t o = j + half * h;
+    const Fe f = fold1<F>(Io::ld(X, o), Io::ld(X, o + 2 * h), r);
+    Io::st(Y, o, f);
+    const Fe lo = shfl_fe(f, (int)(lane & ~1u));        // the group's lo for this table
+    const Fe v = half ? at2<F>(lo, f) : f;               // even: X(0), odd: X(2)
+    const Fe partner = shfl_fe(v, (int)((lane + 2) & 63));
+    wide_mac<F>(acc, v, partner);
+  }
+  return acc;
+}
+// the block's limb sums of those products: e0 -> sc.tot[0..17), e2 -> sc.tot[17..34)
+template <class F>
+__device__ __forceinline__ void lanes_limb_sums(const Wide& acc, LimbScratch<17>& sc) {
+  const uint32_t s = threadIdx.x & 7, half = s & 1;
+  const bool mine = (s & 2u) == 0;  // s in {0, 1, 4, 5}: the product lanes
+  const Wide z = wide_zero<F>();
+  block_limb_sums(mine && half == 0 ? acc : z, sc, 0);
+  block_limb_sums(mine && half == 1 ? acc : z, sc, 17);
+  __syncthreads();
+}
+
 template <class F>
 __global__ __launch_bounds__(kBlock) void k_gkr_round_lanes(const Fe* __restrict__ A, const Fe* __restrict__ S,
                                                             const Fe* __restrict__ M, const Fe* __restrict__ P,
@@ -736,29 +787,14 @@ __global__ __launch_bounds__(kBlock) void k_gkr_round_lanes(const Fe* __restrict
                                                             RoundIn rin, RoundSink sink) {
   ZK_STAMP(0);
   const Fe r = block_get_r(rin);
-  const uint32_t lane = threadIdx.x & 63, s = threadIdx.x & 7, tb = s >> 1, half = s & 1;
+  const uint32_t tb = (threadIdx.x & 7) >> 1;
   const Fe* __restrict__ X = tb == 0 ? A : tb == 1 ? S : tb == 2 ? M : P;
   Fe* __restrict__ Y = tb == 0 ? A2 : tb == 1 ? S2 : tb == 2 ? M2 : P2;
-  Wide acc = wide_zero<F>();  // lanes 0,4: t = 0 products; lanes 1,5: t = 2; others unused
-  const uint64_t stride = (uint64_t)gridDim.x * (kBlock / 8);
-  // the loop bound is uniform per 8-lane group (and per wave: 8 groups share j's stride)
-  for (uint64_t j = ((uint64_t)blockIdx.x * kBlock + threadIdx.x) >> 3; j < h; j += stride) {
-    const uint64_t o = j + half * h;
-    const Fe f = fold1<F>(ld_fe(X, o), ld_fe(X, o + 2 * h), r);
-    st_fold(Y, o, f);
-    const Fe lo = shfl_fe(f, (int)(lane & ~1u));        // the group's lo for this table
-    const Fe v = half ? at2<F>(lo, f) : f;               // even: X(0), odd: X(2)
-    const Fe partner = shfl_fe(v, (int)((lane + 2) & 63));
-    wide_mac<F>(acc, v, partner);
-  }
+  const Wide acc = lanes_pairs<F, PlainIo>(X, Y, h, r, gridDim.x);
   ZK_STAMP(1);
   ZK_STAMP(2);
   __shared__ LimbScratch<17> sc;
-  const bool mine = (s & 2u) == 0;  // s in {0, 1, 4, 5}
-  const Wide z = wide_zero<F>();
-  block_limb_sums(mine && half == 0 ? acc : z, sc, 0);
-  block_limb_sums(mine && half == 1 ? acc : z, sc, 17);
-  __syncthreads();
+  lanes_limb_sums<F>(acc, sc);
   ZK_STAMP(3);
   grid_finish<34>(sc, sink);
 }
@@ -797,75 +833,25 @@ struct TailArgs {
   uint32_t* err;      // pinned error word
   uint64_t* trace;    // debug (ZK_DEBUG_TAIL): per round 8 s_memrealtime stamps, or null
 };
+// slot i of step m's trace row in a persistent kernel with arguments `a`
+// (TailArgs / DTailArgs; tools/trace_print.py names the slots)
 #define ZK_TAIL_STAMP(m, i) \
   do { if (a.trace) a.trace[(m) * 8 + (i)] = __builtin_amdgcn_s_memrealtime(); } while (0)
-
-__device__ __forceinline__ Fe ld_fe_a(const Fe* p, uint64_t i) {
-  const uint64_t* q = reinterpret_cast<const uint64_t*>(p + i);
-  Fe r;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const uint64_t w = __hip_atomic_load(q + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    r.v[2 * k] = (uint32_t)w;
-    r.v[2 * k + 1] = (uint32_t)(w >> 32);
-  }
-  return r;
-}
-__device__ __forceinline__ void st_fe_a(Fe* p, uint64_t i, const Fe& x) {
-  uint64_t* q = reinterpret_cast<uint64_t*>(p + i);
-#pragma unroll
-  for (int k = 0; k < 4; ++k)
-    __hip_atomic_store(q + k, (uint64_t)x.v[2 * k] | ((uint64_t)x.v[2 * k + 1] << 32), __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_AGENT);
-}
 
 template <class F>
 __global__ __launch_bounds__(kBlock) void k_gkr_tail(TailArgs a, RoundSink sink) {
   __shared__ LimbScratch<17> sc;
-  __shared__ Fe s_r;
-  const uint32_t lane = threadIdx.x & 63, s = threadIdx.x & 7, tb = s >> 1, half = s & 1;
-  const bool mine = (s & 2u) == 0;  // s in {0, 1, 4, 5}: the product lanes
+  const uint32_t tb = (threadIdx.x & 7) >> 1;
+  const bool lead = blockIdx.x == 0 && threadIdx.x == 0;
   for (uint32_t m = 0; m < a.nrounds; ++m) {
     const uint64_t h = a.h0 >> m;
     const uint64_t want = (8 * h + kBlock - 1) / kBlock;
     const uint32_t nb = want < gridDim.x ? (uint32_t)want : gridDim.x;
     if (blockIdx.x >= nb) return;  // idle from here on (nb never grows)
-    // ---- challenge r_{k-1}: block 0 polls the host, the others its relay ----
-    if (threadIdx.x == 0) {
-      if (blockIdx.x == 0) ZK_TAIL_STAMP(m, 0);
-      const uint32_t tag = a.rtag0 + m;
-      const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
-      bool ok = true;
-      Fe r;
-      if (blockIdx.x == 0) {
-        while ((int32_t)(__hip_atomic_load(&a.host->tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) - tag) < 0) {
-          __builtin_amdgcn_s_sleep(2);
-          if (__builtin_amdgcn_s_memrealtime() - t0 > kWaitTicks) { ok = false; break; }
-        }
-#pragma unroll
-        for (int i = 0; i < 8; ++i) r.v[i] = __hip_atomic_load(&a.host->r.v[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        if (nb > 1) {
-#pragma unroll
-          for (int i = 0; i < 8; ++i)
-            __hip_atomic_store(&a.relay[m].r.v[i], r.v[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-          __hip_atomic_store(&a.relay[m].tag, tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-      } else {
-        const RWait* rl = a.relay + m;
-        while ((int32_t)(__hip_atomic_load(&rl->tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - tag) < 0) {
-          __builtin_amdgcn_s_sleep(1);
-          if (__builtin_amdgcn_s_memrealtime() - t0 > kWaitTicks) { ok = false; break; }
-        }
-#pragma unroll
-        for (int i = 0; i < 8; ++i) r.v[i] = __hip_atomic_load(&rl->r.v[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      if (!ok) __hip_atomic_store(a.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      s_r = r;
-      if (blockIdx.x == 0) ZK_TAIL_STAMP(m, 1);
-    }
-    __syncthreads();
-    const Fe r = s_r;
+    // ---- challenge r_{k-1}: block 0 polls the host, the others this round's relay slot ----
+    if (lead) ZK_TAIL_STAMP(m, 0);
+    const Fe r = block_wait_r(a.host, a.relay + m, nb > 1, a.rtag0 + m, a.err);
+    if (lead) ZK_TAIL_STAMP(m, 1);
     // ---- fold by r and evaluate e0, e2 (the k_gkr_round_lanes step) ----
     const Fe* X;
     if (m == 0) {
@@ -874,49 +860,19 @@ __global__ __launch_bounds__(kBlock) void k_gkr_tail(TailArgs a, RoundSink sink)
       X = a.out + tail_region(a.h0, m - 1) + (uint64_t)tb * 4 * h;  // previous round: 4 tables of 4h
     }
     Fe* Y = a.out + tail_region(a.h0, m) + (uint64_t)tb * 2 * h;
-    Wide acc = wide_zero<F>();
-    const uint64_t stride = (uint64_t)nb * (kBlock / 8);
-    for (uint64_t j = ((uint64_t)blockIdx.x * kBlock + threadIdx.x) >> 3; j < h; j += stride) {
-      const uint64_t o = j + half * h;
-      const Fe f = fold1<F>(ld_fe_a(X, o), ld_fe_a(X, o + 2 * h), r);
-      st_fe_a(Y, o, f);
-      const Fe lo = shfl_fe(f, (int)(lane & ~1u));
-      const Fe v = half ? at2<F>(lo, f) : f;
-      const Fe partner = shfl_fe(v, (int)((lane + 2) & 63));
-      wide_mac<F>(acc, v, partner);
-    }
+    const Wide acc = lanes_pairs<F, AgentIo>(X, Y, h, r, nb);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's table stores have landed
-    if (blockIdx.x == 0 && threadIdx.x == 0) ZK_TAIL_STAMP(m, 2);
-    const Wide z = wide_zero<F>();
-    block_limb_sums(mine && half == 0 ? acc : z, sc, 0);
-    block_limb_sums(mine && half == 1 ? acc : z, sc, 17);
-    __syncthreads();
+    if (lead) ZK_TAIL_STAMP(m, 2);
+    lanes_limb_sums<F>(acc, sc);
     // ---- fan-in over the nb active blocks, publish ----
     RoundSink sk = sink;
     sk.tag = sink.tag + m;
-    const uint32_t t = threadIdx.x;
-    if (nb > 1) {
-      if (t < 34u) __hip_atomic_fetch_add(sk.accum + t, sc.tot[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      if (t == 0) {
-        const uint32_t prev = __hip_atomic_fetch_add(sk.counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        sc.am_last = prev == nb - 1;
-      }
-      __syncthreads();
-      if (sc.am_last) {
-        if (t == 0) ZK_TAIL_STAMP(m, 3);
-        if (t < 34u) sc.tot[t] = __hip_atomic_exchange(sk.accum + t, (uint64_t)0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (t == 0) __hip_atomic_store(sk.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        publish_limbs<34>(sc, sk);
-        if (t == 0) ZK_TAIL_STAMP(m, 4);
-      }
-    } else {
-      if (t == 0) ZK_TAIL_STAMP(m, 3);
+    if (nb == 1 || atomic_fan_in<34>(sc, sk, nb)) {
+      if (threadIdx.x == 0) ZK_TAIL_STAMP(m, 3);
       publish_limbs<34>(sc, sk);
-      if (t == 0) ZK_TAIL_STAMP(m, 4);
+      if (threadIdx.x == 0) ZK_TAIL_STAMP(m, 4);
     }
-    __syncthreads();  // sc and s_r are reused next round
+    __syncthreads();  // sc and the challenge's LDS copy are reused next round
   }
 }
 
@@ -1105,6 +1061,56 @@ __device__ __forceinline__ void dround_limb_sums(const Wide& acc, DScratch& sc) 
   }
   __syncthreads();
 }
+// A thread's place in a double step. Wave w: product w & 1 (A*S or M*P), quads
+// (w >> 1) * 8 + [0, 8) of each kDQuads; lane = 8 unit + 4 tab + k.
+struct DLanes {
+  uint32_t k, tab, pp, jl;  // corner, table of the product, product, quad of the block's 16
+  __device__ __forceinline__ DLanes() {
+    const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    k = lane & 3, tab = (lane >> 2) & 1, pp = wv & 1, jl = (wv >> 1) * 8 + (lane >> 3);
+  }
+  __device__ __forceinline__ uint32_t table() const { return 2 * pp + tab; }  // 0..3: A, S, M, P
+  template <class T>
+  __device__ __forceinline__ T* pick(T* a, T* s, T* m, T* p) const { return pp ? (tab ? p : m) : (tab ? s : a); }
+};
+// The step over Q quads by nb blocks: every lane folds its corner of table X
+// (4 NP tables' worth: 16 Q or 8 Q elements) by the pending challenges into X2
+// (4Q), or, with H2, into the word-major host table (st_fe_sys below), and
+// multiplies. two: NP = 2, the fold by (ra, rb) through the constants of
+// (ra, rb, ra rb) in ct[30]; else the fold by rb alone, whose constants are
+// block 1 of ct[30] or all of ct[10]. Returns the lane's product sum
+// (category 2k + tab).
+template <class F, class Io, int NC>
+__device__ __forceinline__ Wide dstep_quads(const DLanes& L, const Fe* __restrict__ X, Fe* __restrict__ X2, uint64_t* H2,
+                                            uint64_t Q, uint32_t nb, bool two, const Fe (&ct)[NC]) {
+  static_assert(NC == 30 || NC == 10, "constants of (ra, rb, ra rb) or of rb");
+  const uint64_t h4 = 4 * Q;
+  Wide acc = wide_zero<F>();
+  for (uint64_t jb = (uint64_t)blockIdx.x * kDQuads; jb < Q; jb += (uint64_t)nb * kDQuads) {
+    const uint64_t j = jb + L.jl;
+    if (j < Q) {  // uniform over the 8 lanes of a unit
+      const uint64_t i = j + L.k * Q;
+      Fe z;
+      if (two) {
+        if constexpr (NC == 30) {
+          const Fe x00 = Io::ld(X, i), x01 = Io::ld(X, i + h4), x10 = Io::ld(X, i + 2 * h4), x11 = Io::ld(X, i + 3 * h4);
+          Io::loads_first();
+          z = fold2c<F>(x00, x01, x10, x11, ct);
+        }
+      } else {
+        const Fe x0 = Io::ld(X, i), x1 = Io::ld(X, i + h4);
+        Io::loads_first();
+        z = fold1c<F, NC == 30 ? 1 : 0>(x0, x1, ct);
+      }
+      if (H2)
+        st_fe_sys(H2, h4, i, z);
+      else
+        Io::st(X2, i, z);
+      unit_product<F>(z, L.k, L.tab, acc);
+    }
+  }
+  return acc;
+}
 
 template <class F, int NP>
 __global__ __launch_bounds__(kBlock) void k_gkr_dround(const Fe* __restrict__ A, const Fe* __restrict__ S,
@@ -1123,31 +1129,10 @@ __global__ __launch_bounds__(kBlock) void k_gkr_dround(const Fe* __restrict__ A,
   else
     fold_consts<F, NP == 2 ? 3 : 1>(rb, rb, rb, ct);
   __shared__ DScratch sc;
-  // wave w: product w & 1 (A*S or M*P), quads (w >> 1) * 8 + [0, 8) of each 16; lane = 8 unit + 4 tab + k
-  const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6, k = lane & 3, tab = (lane >> 2) & 1;
-  const uint32_t pp = wv & 1, jl = (wv >> 1) * 8 + (lane >> 3);
-  const Fe* __restrict__ X = pp ? (tab ? P : M) : (tab ? S : A);
-  Fe* __restrict__ X2 = pp ? (tab ? P2 : M2) : (tab ? S2 : A2);
-  const uint64_t h4 = 4 * Q;
-  Wide acc = wide_zero<F>();
-  for (uint64_t jb = (uint64_t)blockIdx.x * kDQuads; jb < Q; jb += (uint64_t)gridDim.x * kDQuads) {
-    const uint64_t j = jb + jl;
-    if (j < Q) {  // uniform over the 8 lanes of a unit
-      const uint64_t i = j + k * Q;
-      Fe z;
-      if constexpr (NP == 2) {
-        const Fe x00 = ld_fe(X, i), x01 = ld_fe(X, i + h4), x10 = ld_fe(X, i + 2 * h4), x11 = ld_fe(X, i + 3 * h4);
-        __builtin_amdgcn_sched_barrier(0);  // issue all loads before any arithmetic
-        z = fold2c<F>(x00, x01, x10, x11, ct);
-      } else {
-        const Fe x0 = ld_fe(X, i), x1 = ld_fe(X, i + h4);
-        __builtin_amdgcn_sched_barrier(0);
-        z = fold1c<F, 0>(x0, x1, ct);
-      }
-      st_fold(X2, i, z);
-      unit_product<F>(z, k, tab, acc);
-    }
-  }
+  const DLanes L;
+  const Fe* __restrict__ X = L.pick(A, S, M, P);
+  Fe* __restrict__ X2 = L.pick(A2, S2, M2, P2);
+  const Wide acc = dstep_quads<F, PlainIo>(L, X, X2, nullptr, Q, gridDim.x, NP == 2, ct);
   dround_limb_sums(acc, sc);
   grid_finish<kDLimbs>(sc, sink);
 }
@@ -1195,13 +1180,7 @@ struct DTailArgs {
 // element-major 8-byte stores crossed the host link one by one, ~20 ns each);
 // every storing wave drains (vmcnt(0)) before its block counts in, so the flag
 // the last block raises comes after every table store has completed: the host
-// runs the remaining rounds on them (host.hpp "host rounds").
-__device__ __forceinline__ void st_fe_sys(uint64_t* p, uint64_t n, uint64_t i, const Fe& x) {
-#pragma unroll
-  for (int k = 0; k < 4; ++k)
-    __hip_atomic_store(p + k * n + i, (uint64_t)x.v[2 * k] | ((uint64_t)x.v[2 * k + 1] << 32), __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_SYSTEM);
-}
+// runs the remaining rounds on them (host.hpp "host rounds"): st_fe_sys.
 
 // DFS (ZK_DEVICE_FS=1, dfs.hpp): every step but the last draws the next
 // step's challenges on the device. The host posts step 0's (ra, rb, rab), the
@@ -1216,9 +1195,9 @@ __global__ __launch_bounds__(kBlock) void k_gkr_dtail(DTailArgs a, RoundSink sin
   __shared__ DScratch sc;
   __shared__ Fe ct[30];
   __shared__ uint32_t s_w[kFsWords];  // (DFS) the step's relay words
-  const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6, k = lane & 3, tab = (lane >> 2) & 1;
-  const uint32_t pp = wv & 1, jl = (wv >> 1) * 8 + (lane >> 3);
-  const uint32_t tb = 2 * pp + tab;  // table A, S, M, P
+  const DLanes L;
+  const uint32_t tb = L.table();
+  const bool lead = blockIdx.x == 0 && threadIdx.x == 0;
   for (uint32_t st = 0; st < a.nsteps; ++st) {
     const uint64_t Q = a.Q0 >> (2 * st);
     const uint64_t want = (Q + kDQuads - 1) / kDQuads;
@@ -1233,7 +1212,7 @@ __global__ __launch_bounds__(kBlock) void k_gkr_dtail(DTailArgs a, RoundSink sin
     din.err = a.err;
     din.tag = a.rtag0 + st;
     Fe ra, rb, rab;
-    if (a.trace && blockIdx.x == 0 && threadIdx.x == 0) a.trace[st * 8 + 0] = __builtin_amdgcn_s_memrealtime();
+    if (lead) ZK_TAIL_STAMP(st, 0);
     if constexpr (DFS) {
       block_get_words<kFsWords / 8>(din, s_w, nb > 1, st > 0);
 #pragma unroll
@@ -1245,11 +1224,10 @@ __global__ __launch_bounds__(kBlock) void k_gkr_dtail(DTailArgs a, RoundSink sin
     } else {
       block_get_rs(din, ra, rb, rab, nb > 1);
     }
-    if (a.trace && blockIdx.x == 0 && threadIdx.x == 0) a.trace[st * 8 + 1] = __builtin_amdgcn_s_memrealtime();
+    if (lead) ZK_TAIL_STAMP(st, 1);
     const bool two = st > 0 || a.np0 == 2;
     fold_consts<F, 3>(ra, rb, rab, ct);  // blocks 0, 1, 2: ra, rb, ra rb
-    if (a.trace && blockIdx.x == 0 && threadIdx.x == 0) a.trace[st * 8 + 6] = __builtin_amdgcn_s_memrealtime();
-    const uint64_t h4 = 4 * Q;
+    if (lead) ZK_TAIL_STAMP(st, 6);
     const Fe* X;
     if (st == 0) {
       X = a.in[tb];
@@ -1259,47 +1237,18 @@ __global__ __launch_bounds__(kBlock) void k_gkr_dtail(DTailArgs a, RoundSink sin
     }
     Fe* X2 = a.out + dtail_region(a.Q0, st) + (uint64_t)tb * 4 * Q;
     uint64_t* H2 = a.host_tab && st + 1 == a.nsteps ? a.host_tab + (uint64_t)tb * 16 * Q : nullptr;
-    Wide acc = wide_zero<F>();
-    for (uint64_t jb = (uint64_t)blockIdx.x * kDQuads; jb < Q; jb += (uint64_t)nb * kDQuads) {
-      const uint64_t j = jb + jl;
-      if (j < Q) {
-        const uint64_t i = j + k * Q;
-        const Fe z = two ? fold2c<F>(ld_fe_a(X, i), ld_fe_a(X, i + h4), ld_fe_a(X, i + 2 * h4), ld_fe_a(X, i + 3 * h4), ct)
-                         : fold1c<F, 1>(ld_fe_a(X, i), ld_fe_a(X, i + h4), ct);
-        if (H2)
-          st_fe_sys(H2, 4 * Q, i, z);
-        else
-          st_fe_a(X2, i, z);
-        unit_product<F>(z, k, tab, acc);
-      }
-    }
-    if (a.trace && blockIdx.x == 0 && threadIdx.x == 0) a.trace[st * 8 + 7] = __builtin_amdgcn_s_memrealtime();
+    const Wide acc = dstep_quads<F, AgentIo>(L, X, X2, H2, Q, nb, two, ct);
+    if (lead) ZK_TAIL_STAMP(st, 7);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's table stores have landed
-    if (a.trace && blockIdx.x == 0 && threadIdx.x == 0) a.trace[st * 8 + 2] = __builtin_amdgcn_s_memrealtime();
+    if (lead) ZK_TAIL_STAMP(st, 2);
     dround_limb_sums(acc, sc);
-    if (a.trace && blockIdx.x == 0 && threadIdx.x == 0) a.trace[st * 8 + 3] = __builtin_amdgcn_s_memrealtime();
+    if (lead) ZK_TAIL_STAMP(st, 3);
     RoundSink sk = sink;
     sk.tag = sink.tag + st;
     const uint32_t t = threadIdx.x;
-    bool last = true;  // this block holds the step's totals in sc.tot
-    if (nb > 1) {
-      if (t < (uint32_t)kDLimbs) __hip_atomic_fetch_add(sk.accum + t, sc.tot[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      if (t == 0) {
-        const uint32_t prev = __hip_atomic_fetch_add(sk.counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        sc.am_last = prev == nb - 1;
-      }
-      __syncthreads();
-      last = sc.am_last;
-      if (last) {
-        if (t < (uint32_t)kDLimbs)
-          sc.tot[t] = __hip_atomic_exchange(sk.accum + t, (uint64_t)0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (t == 0) __hip_atomic_store(sk.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-    }
-    if (last) {
-      if (a.trace && t == 0) a.trace[st * 8 + 4] = __builtin_amdgcn_s_memrealtime();
+    // (a single block holds the step's totals in sc.tot already)
+    if (nb == 1 || atomic_fan_in<kDLimbs>(sc, sk, nb)) {
+      if (t == 0) ZK_TAIL_STAMP(st, 4);
       if (DFS && st + 1 < a.nsteps) {
         __syncthreads();  // sc.tot complete
         if (t < 64) {  // wave 0: both rounds' Fiat-Shamir, then the next step's relay words
@@ -1327,7 +1276,7 @@ __global__ __launch_bounds__(kBlock) void k_gkr_dtail(DTailArgs a, RoundSink sin
       } else {
         publish_limbs<kDLimbs>(sc, sk);
       }
-      if (a.trace && t == 0) a.trace[st * 8 + 5] = __builtin_amdgcn_s_memrealtime();
+      if (t == 0) ZK_TAIL_STAMP(st, 5);
     }
     __syncthreads();  // sc is reused next step
   }
@@ -1352,8 +1301,8 @@ __global__ __launch_bounds__(kBlock) void k_sc_round(const Fe* __restrict__ X, F
     } else {
       const Fe x0 = ld_fe(X, j), x1 = ld_fe(X, j + h), x2 = ld_fe(X, j + 2 * h), x3 = ld_fe(X, j + 3 * h);
       const Fe f0 = fold1<F>(x0, x2, r), f1 = fold1<F>(x1, x3, r);
-      st_fold(Y, j, f0);
-      st_fold(Y, j + h, f1);
+      st_fe(Y, j, f0);
+      st_fe(Y, j + h, f1);
       acc[0] = fe_add<F>(acc[0], f0);
       acc[1] = fe_add<F>(acc[1], f1);
     }

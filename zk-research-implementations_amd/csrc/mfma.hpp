@@ -600,7 +600,7 @@ __global__ __launch_bounds__(kBlock, 2) void k_gkr_dm(const Fe* __restrict__ A, 
         dm_load(X, (ch + gridDim.x) * kDMQuads + l, h4, in);
       z[k] = dm_fold<F>(cur, wf);
       ZK_DCHECK(j + k * Q < 4 * Q);
-      st_fold(X2, j + k * Q, z[k]);
+      st_fe(X2, j + k * Q, z[k]);
     }
     dm_products<F>(z, sc, acc);
   }
@@ -932,7 +932,7 @@ __global__ __launch_bounds__(kBlock, 2) void k_gkr_dm3(const Fe* __restrict__ A,
       }
       z[k] = fold8<F>(x, wf);
       ZK_DCHECK(j + k * Q < 4 * Q);
-      st_fold(X2, j + k * Q, z[k]);
+      st_fe(X2, j + k * Q, z[k]);
     }
     dm_products<F>(z, sc, acc);
   }
@@ -1037,7 +1037,7 @@ struct T33Io {
   __device__ __forceinline__ void store(uint64_t ch, int f, const Fe& z) const {
     const uint64_t e = out_at(pch(ch), f);
     ZK_DCHECK(e < 8 * O);
-    st_fold(X2, e, z);
+    st_fe(X2, e, z);
   }
 };
 
