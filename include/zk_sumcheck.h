@@ -369,6 +369,58 @@ int zk_dev_gkr_sumcheck_prove(zk_ctx* ctx, zk_field field, const void* const d_t
                               zk_fe* out_coeffs, uint8_t* out_ncoeffs, zk_fe* out_challenges);
 
 /* ---------------------------------------------------------------------------
+ * Keccak Merkle tree over field elements — merkle_tree/src/merkle_tree.rs
+ * (MerkleTree<F> :25-29). With LE32 the canonical 32-byte image:
+ *   compute_hash(x) = from_le_bytes_mod_order(Keccak256(LE32(x)))            :201-206
+ *   hash_pair(l, r) = from_le_bytes_mod_order(Keccak256(LE32(l) | LE32(r)))  :208-214
+ * leaves has 2^depth entries, tree[level] has 2^(depth-1-level) nodes, tree[0]
+ * holds the parents of the leaves, the root is tree[depth-1][0]. The whole
+ * tree lives in device memory ((2^(depth+1) - 1) * 32 B, one allocation; a
+ * failed allocation is ZK_EDEVICE) and every hash runs on the GPU.
+ * Where the reference returns Err or would panic the call returns ZK_EINVAL and
+ * writes nothing: depth = 0 (get_root_hash indexes depth - 1), too many
+ * inputs, a leaf id >= 2^depth, data that does not match the leaf, and any
+ * value >= p. A tree belongs to its context: free it before the context.
+ *   zk_merkle_new      new :32-52 (n_inputs = 0: all leaves the element 0, not
+ *                      hashed) / new_with_inputs :54-82 (leaves[i] =
+ *                      compute_hash(inputs[i]), the rest 0)
+ *   zk_dev_merkle_new  new_with_inputs over a table already on the device
+ *                      (Montgomery elements, as zk_dev_upload leaves them)
+ *   zk_merkle_root     get_root_hash :134-136
+ *   zk_merkle_download the leaves (level = -1) or tree[level] (0 .. depth-1)
+ *   zk_merkle_update_leaves  update_leaf :84-104 for n leaves at once (is_hash[i]
+ *                      != 0: the leaf becomes data[i], else compute_hash(data[i]));
+ *                      every path is recomputed :106-132. The reference is
+ *                      sequential, so ids must be distinct (else ZK_EINVAL)
+ *   zk_merkle_create_proofs  create_proof :138-183 for n leaves, all or nothing:
+ *                      out_siblings[i*depth + level] / out_sides[i*depth + level]
+ *                      from the leaf level upward; side 0 = LeafSide::Left,
+ *                      1 = Right (Right when the running index is even :165-169)
+ * Host only (no context), as zk_gkr_sumcheck_verify:
+ *   zk_merkle_hash_leaf / zk_merkle_hash_pair   compute_hash / hash_pair
+ *   zk_merkle_verify_proof  verify :185-199 against a given root: folds
+ *                      compute_hash(data) with the len entries; *out_ok = 1 / 0.
+ *                      As in the reference, len is not checked against a depth;
+ *                      a side other than 0 / 1 is ZK_EINVAL
+ * ------------------------------------------------------------------------- */
+typedef struct zk_merkle zk_merkle;
+int zk_merkle_new(zk_ctx* ctx, zk_field field, uint32_t depth, zk_repr repr, const zk_fe* inputs, uint64_t n_inputs,
+                  zk_merkle** out);
+int zk_dev_merkle_new(zk_ctx* ctx, zk_field field, uint32_t depth, const void* dev_inputs, uint64_t n_inputs,
+                      zk_merkle** out);
+void zk_merkle_free(zk_merkle* tree);
+int zk_merkle_root(zk_merkle* tree, zk_repr repr, zk_fe* out);
+int zk_merkle_download(zk_merkle* tree, int level, zk_repr repr, zk_fe* out);
+int zk_merkle_update_leaves(zk_merkle* tree, zk_repr repr, const uint64_t* ids, const zk_fe* data,
+                            const uint8_t* is_hash, size_t n);
+int zk_merkle_create_proofs(zk_merkle* tree, zk_repr repr, const zk_fe* data, const uint64_t* ids, size_t n,
+                            zk_fe* out_siblings /* n*depth */, uint8_t* out_sides /* n*depth */);
+int zk_merkle_hash_leaf(zk_field field, zk_repr repr, const zk_fe* x, zk_fe* out);
+int zk_merkle_hash_pair(zk_field field, zk_repr repr, const zk_fe* left, const zk_fe* right, zk_fe* out);
+int zk_merkle_verify_proof(zk_field field, zk_repr repr, const zk_fe* root, const zk_fe* data, const zk_fe* siblings,
+                           const uint8_t* sides, size_t len, int* out_ok);
+
+/* ---------------------------------------------------------------------------
  * Multi-GPU: the hypercube is split over `world` ranks (one process or thread
  * per GPU, world a power of two). Rank g holds the sub-cube whose LOW
  * log2(world) index bits equal g: local m <-> global m*world + g. The first

@@ -5,6 +5,7 @@ Python mirror of the reference crates' API (obah/zk-research-implementations):
   multilinear_polynomial::{MultilinearPoly, ProductPoly, SumPoly}
   univariate_polynomial::UnivariatePoly
   sum_check::sum_check_protocol::{prove, verify, gkr_prove, gkr_verify, Proof, GkrProof, GkrVerify}
+  merkle_tree::{MerkleTree, MerkleProof, ProofData, LeafSide}  (zk_amd.merkle)
 over the C ABI of include/zk_sumcheck.h. Every table-sized operation runs in
 the HIP library on a gfx950 GPU; this module only marshals arguments.
 
@@ -36,4 +37,6 @@ from .api import (  # noqa: F401
 )
 from .context import Context, DeviceTable  # noqa: F401
 from . import gkr  # noqa: F401  (gkr crate mirror: Circuit, Operation, prove, verify)
+from . import merkle  # noqa: F401  (merkle_tree crate mirror)
+from .merkle import LeafSide, MerkleProof, MerkleTree, ProofData  # noqa: F401
 from ._lib import ZkError  # noqa: F401

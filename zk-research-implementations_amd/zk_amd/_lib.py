@@ -110,6 +110,16 @@ SIGNATURES = {
     "zk_dev_mle_partial_evaluate": (I, [P, I, P, U32, U32, I, P, P]),
     "zk_dev_mle_tensor": (I, [P, I, I, P, U64, P, U64, P]),
     "zk_dev_gkr_sumcheck_prove": (I, [P, I, P, U32, I, P, P, P, P, P]),
+    "zk_merkle_new": (I, [P, I, U32, I, P, U64, C.POINTER(C.c_void_p)]),
+    "zk_dev_merkle_new": (I, [P, I, U32, P, U64, C.POINTER(C.c_void_p)]),
+    "zk_merkle_free": (None, [P]),
+    "zk_merkle_root": (I, [P, I, P]),
+    "zk_merkle_download": (I, [P, I, I, P]),
+    "zk_merkle_update_leaves": (I, [P, I, P, P, P, SZ]),
+    "zk_merkle_create_proofs": (I, [P, I, P, P, SZ, P, P]),
+    "zk_merkle_hash_leaf": (I, [I, I, P, P]),
+    "zk_merkle_hash_pair": (I, [I, I, P, P, P]),
+    "zk_merkle_verify_proof": (I, [I, I, P, P, P, P, SZ, C.POINTER(C.c_int)]),
     "zk_ctx_attach_host_comm": (I, [P, I, I, ALLREDUCE_FN, P]),
     "zk_comm_get_unique_id": (I, [P]),
     "zk_ctx_attach_rccl": (I, [P, I, I, P]),
