@@ -421,6 +421,52 @@ int zk_merkle_verify_proof(zk_field field, zk_repr repr, const zk_fe* root, cons
                            const uint8_t* sides, size_t len, int* out_ok);
 
 /* ---------------------------------------------------------------------------
+ * FFT — fft/src/fft.rs: the radix-2 number-theoretic transform over a scalar
+ * field and the polynomial product built on it. With w = F::get_root_of_unity(n)
+ *   evaluate     y[k] = sum_j c[j] w^(jk)                       (dft :6-29, :31-41)
+ *   interpolate  c[j] = n^-1 sum_k y[k] w^(-jk), all n of them, untrimmed  (:43-60)
+ * both in natural order on both sides. The result is an exact field element, so
+ * it equals the reference's bit for bit whatever the algorithm; here every
+ * butterfly runs on the GPU, in ceil(log2 n / 8) passes over the table.
+ * The root is defined for n a power of two up to 2^s, s the field's
+ * two-adicity (BN254 Fr 28, BLS12-381 Fr 32, BN254 Fq 1): F::TWO_ADIC_ROOT_OF_UNITY
+ * squared s - log2 n times. (ark's get_root_of_unity also knows 3 2^k and
+ * 9 2^k through a small subgroup; fft.rs panics on those lengths before it
+ * asks, so they are ZK_EINVAL here.)
+ * ZK_EINVAL, where the reference panics: n = 0 or not a power of two, log2 n
+ * above the two-adicity, a value >= p, a null pointer. ZK_EUNSUPPORTED: log2 n
+ * > 28 (a 2^28 table is 8 GiB). Sizes above 2^24 (2^23-term operands for the
+ * product) have not been measured or tested.
+ *   zk_fft_root_of_unity        F::get_root_of_unity(n) (host)
+ *   zk_fft_interpolation_roots  get_interpolation_roots :70-78 (host): the
+ *                      reference's GeneralEvaluationDomain::new(n) rounds n up to
+ *                      N = next_power_of_two(n); out[k] = w_N^(-k) N^-1, k < n, for
+ *                      any n >= 1. ZK_EINVAL when N exceeds the two-adicity or 2^28
+ *   zk_fft_evaluate    fft_evaluate :31-41
+ *   zk_fft_interpolate fft_interpolate :43-60
+ *   zk_dev_fft         the same transform (inverse != 0: interpolate) over a
+ *                      table already on the device (Montgomery elements, as
+ *                      zk_dev_upload leaves them). d_in is only read; d_out is
+ *                      d_in itself or does not overlap it (else ZK_EINVAL)
+ *   zk_poly_mul        impl Mul, univariate_polynomial_dense.rs:95-109: both
+ *                      operands trimmed of trailing zeros as degree() does (:28-32;
+ *                      a zero polynomial is ZK_EINVAL, its len() - 1 underflow);
+ *                      *out_len = deg a + deg b + 1 values to out (cap < *out_len:
+ *                      ZK_EINVAL with *out_len set). Computed as two forward
+ *                      transforms of N = next_power_of_two(*out_len) points, a
+ *                      pointwise product and one inverse, all on the device; an N
+ *                      above the two-adicity or 2^28 is ZK_EUNSUPPORTED (BN254 Fq:
+ *                      every product longer than 2)
+ * ------------------------------------------------------------------------- */
+int zk_fft_root_of_unity(zk_field field, zk_repr repr, uint64_t n, zk_fe* out);
+int zk_fft_interpolation_roots(zk_field field, zk_repr repr, uint64_t n, zk_fe* out /* n */);
+int zk_fft_evaluate(zk_ctx* ctx, zk_field field, zk_repr repr, const zk_fe* coeffs, uint64_t n, zk_fe* out /* n */);
+int zk_fft_interpolate(zk_ctx* ctx, zk_field field, zk_repr repr, const zk_fe* evals, uint64_t n, zk_fe* out /* n */);
+int zk_dev_fft(zk_ctx* ctx, zk_field field, const void* d_in, uint64_t n, int inverse, void* d_out);
+int zk_poly_mul(zk_ctx* ctx, zk_field field, zk_repr repr, const zk_fe* a, uint64_t na, const zk_fe* b, uint64_t nb,
+                zk_fe* out, uint64_t cap, uint64_t* out_len);
+
+/* ---------------------------------------------------------------------------
  * Multi-GPU: the hypercube is split over `world` ranks (one process or thread
  * per GPU, world a power of two). Rank g holds the sub-cube whose LOW
  * log2(world) index bits equal g: local m <-> global m*world + g. The first

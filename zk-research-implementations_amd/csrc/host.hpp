@@ -25,6 +25,7 @@
 #include "mfma.hpp"
 #include "gkr_plan.hpp"
 #include "gkr_rounds.hpp"
+#include "fft_plan.hpp"
 
 using zk::Fe;
 
@@ -145,6 +146,17 @@ struct ScopedBuf {
   ~ScopedBuf() { b.release(); }
 };
 
+// The twiddle tables of one transform shape (fft.hip), built on the host once
+// and kept for the context's life.
+struct FftTables {
+  int field = 0;
+  uint32_t m = 0;
+  bool inverse = false;
+  uint32_t log_w = 0, h = 0;
+  DevBuf stage_roots, hi, lo, lo_scaled;
+  Fe n_inv;
+};
+
 enum CommKind { COMM_NONE = 0, COMM_HOST = 1, COMM_RCCL = 2 };
 }  // namespace zkh
 using namespace zkh;
@@ -228,6 +240,11 @@ struct zk_ctx {
   DevBuf scan_tmp[4];
   DevBuf g1_table;
   DevBuf g1_table16;  // 16-bit windows (100 MB), built on the device from g1_table
+  // NTT (fft.hip): stages per pass (ZK_FFT_STAGES, 1 .. kFftTileLog), the passes'
+  // ping-pong scratch (grow-only) and the twiddle tables per (field, log2 n, direction)
+  uint32_t fft_stages = kFftTileLog;
+  DevBuf fft_scratch[2];
+  std::vector<std::unique_ptr<FftTables>> fft_tables;
   // (the 20-bit signed-window table, 654 MB, is cached per device for the process: kzg.hip FixedBaseCache)
 };
 

@@ -56,6 +56,7 @@ int zk_ctx_create(int device, zk_ctx** out) {
     if (const char* e = getenv("ZK_CIRCUIT_HOST_LGL")) c->circuit_host_lgl = (uint32_t)strtoul(e, nullptr, 0);
     if (const char* e = getenv("ZK_DTAIL_MAX_QUADS")) c->dtail_max_quads = strtoull(e, nullptr, 0);
     if (const char* e = getenv("ZK_GRID_CAP")) c->grid_cap = (uint32_t)strtoul(e, nullptr, 0);
+    if (const char* e = getenv("ZK_FFT_STAGES")) c->fft_stages = fft_stage_cap(strtol(e, nullptr, 0));
     if (const char* e = getenv("ZK_ATOMIC_FANIN")) c->atomic_fanin = (uint32_t)strtoul(e, nullptr, 0);
     if (const char* e = getenv("ZK_DTAIL_BLOCKS")) c->dtail_blocks = (uint32_t)strtoul(e, nullptr, 0);
     if (const char* e = getenv("ZK_GATHER_VARS")) c->gather_vars = (uint32_t)strtoul(e, nullptr, 0);
@@ -118,6 +119,13 @@ void zk_ctx_destroy(zk_ctx* c) {
   for (auto& b : c->scan_tmp) b.release();
   c->g1_table.release();
   c->g1_table16.release();
+  for (auto& b : c->fft_scratch) b.release();
+  for (auto& t : c->fft_tables) {
+    t->stage_roots.release();
+    t->hi.release();
+    t->lo.release();
+    t->lo_scaled.release();
+  }
   if (c->h_red) (void)hipHostFree(c->h_red);
   if (c->h_tab) (void)hipHostFree(c->h_tab);
   if (c->h_fslog) (void)hipHostFree(c->h_fslog);

@@ -6,6 +6,7 @@ Python mirror of the reference crates' API (obah/zk-research-implementations):
   univariate_polynomial::UnivariatePoly
   sum_check::sum_check_protocol::{prove, verify, gkr_prove, gkr_verify, Proof, GkrProof, GkrVerify}
   merkle_tree::{MerkleTree, MerkleProof, ProofData, LeafSide}  (zk_amd.merkle)
+  fft::{fft_evaluate, fft_interpolate, split_poly, get_interpolation_roots}  (zk_amd.fft)
 over the C ABI of include/zk_sumcheck.h. Every table-sized operation runs in
 the HIP library on a gfx950 GPU; this module only marshals arguments.
 
@@ -39,4 +40,14 @@ from .context import Context, DeviceTable  # noqa: F401
 from . import gkr  # noqa: F401  (gkr crate mirror: Circuit, Operation, prove, verify)
 from . import merkle  # noqa: F401  (merkle_tree crate mirror)
 from .merkle import LeafSide, MerkleProof, MerkleTree, ProofData  # noqa: F401
+from . import fft  # noqa: F401  (fft crate mirror, polynomial product)
+from .fft import (  # noqa: F401
+    dev_fft,
+    fft_evaluate,
+    fft_interpolate,
+    get_interpolation_roots,
+    get_root_of_unity,
+    poly_mul,
+    split_poly,
+)
 from ._lib import ZkError  # noqa: F401

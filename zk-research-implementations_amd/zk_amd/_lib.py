@@ -120,6 +120,12 @@ SIGNATURES = {
     "zk_merkle_hash_leaf": (I, [I, I, P, P]),
     "zk_merkle_hash_pair": (I, [I, I, P, P, P]),
     "zk_merkle_verify_proof": (I, [I, I, P, P, P, P, SZ, C.POINTER(C.c_int)]),
+    "zk_fft_root_of_unity": (I, [I, I, U64, P]),
+    "zk_fft_interpolation_roots": (I, [I, I, U64, P]),
+    "zk_fft_evaluate": (I, [P, I, I, P, U64, P]),
+    "zk_fft_interpolate": (I, [P, I, I, P, U64, P]),
+    "zk_dev_fft": (I, [P, I, P, U64, I, P]),
+    "zk_poly_mul": (I, [P, I, I, P, U64, P, U64, P, U64, C.POINTER(U64)]),
     "zk_ctx_attach_host_comm": (I, [P, I, I, ALLREDUCE_FN, P]),
     "zk_comm_get_unique_id": (I, [P]),
     "zk_ctx_attach_rccl": (I, [P, I, I, P]),

@@ -304,6 +304,35 @@ class UnivariatePoly:
             raise ValueError("attempt to subtract with overflow")
         return len(self.coefficient) - 1
 
+    def scalar_mul(self, scalar: int) -> "UnivariatePoly":  # :34-46 (trimmed)
+        p = modulus(self.field)
+        out = [c * scalar % p for c in self.coefficient]
+        while out and out[-1] == 0:
+            out.pop()
+        return UnivariatePoly(out, self.field)
+
+    def __add__(self, other: "UnivariatePoly") -> "UnivariatePoly":  # impl Add :77-93 (untrimmed)
+        if not isinstance(other, UnivariatePoly):
+            return NotImplemented
+        if int(self.field) != int(other.field):
+            raise ValueError("the summands are over different fields")
+        p = modulus(self.field)
+        out = [0] * max(len(self.coefficient), len(other.coefficient))
+        for i, c in enumerate(self.coefficient):
+            out[i] = c % p
+        for i, c in enumerate(other.coefficient):
+            out[i] = (out[i] + c) % p
+        return UnivariatePoly(out, self.field)
+
+    def __mul__(self, other: "UnivariatePoly") -> "UnivariatePoly":  # impl Mul :95-109, on the device (zk_amd.fft)
+        if not isinstance(other, UnivariatePoly):
+            return NotImplemented
+        from .fft import poly_mul
+
+        self.degree()  # both operands end up trimmed, as the reference's `mut self`, `mut other`
+        other.degree()
+        return poly_mul(self, other)
+
 
 # ---------------------------------------------------------------------------
 # sum_check
