@@ -467,6 +467,46 @@ int zk_poly_mul(zk_ctx* ctx, zk_field field, zk_repr repr, const zk_fe* a, uint6
                 zk_fe* out, uint64_t cap, uint64_t* out_len);
 
 /* ---------------------------------------------------------------------------
+ * Univariate polynomials over arbitrary points —
+ * univariate_polynomial_dense.rs evaluate :20-26 and interpolate :48-74, which
+ * are also all the arithmetic of the shamir_secret_sharing crate. Any field;
+ * no evaluation domain is involved. Results are exact field elements: the
+ * interpolant of n points with distinct x is unique, so it is bit-identical to
+ * the reference's loop, trailing zeros trimmed (:71).
+ *   zk_poly_evaluate      out[i] = sum_k coeffs[k] xs[i]^k, i < npoints, host
+ *                         memory in and out. ncoeffs = 0: 0 everywhere (the
+ *                         empty sum); npoints = 0: a successful no-op
+ *   zk_dev_poly_evaluate  the same over device tables (Montgomery elements, as
+ *                         zk_dev_upload leaves them); nothing crosses the host
+ *                         boundary. out_tbl may be xs_tbl itself; any other
+ *                         overlap with an input is ZK_EINVAL
+ *   zk_poly_eval_plan     how an evaluation of that shape runs on this
+ *                         context's device: *out_chunks runs of *out_chunk_len
+ *                         coefficients each (1: one kernel; more: per-run cells
+ *                         and a combining kernel). Host only
+ *   zk_poly_interpolate   the polynomial of degree < n through (xs[i], ys[i]):
+ *                         *out_ncoeffs <= n trimmed coefficients to out_coeffs
+ *                         (n = 0: none; every y = 0: none). cap < n: ZK_EINVAL
+ * ZK_EINVAL: a null buffer, an unknown field or representation, a value >= p,
+ * two points with the same x (the reference divides by zero, :62-64).
+ * ZK_EUNSUPPORTED: interpolation of more than 2^16 points (about 2.5 n^2 field
+ * products: 10^10 at the cap); evaluation with more than 2^28 coefficients or
+ * points, or npoints x ncoeffs above 2^40 (about ten seconds of products at
+ * the measured 116 G/s). Sizes, field and representation are checked before
+ * the context, the context before any value is read.
+ * Calls with at most ZK_POLY_HOST_MAX points (read at zk_ctx_create; default
+ * 96; evaluations: npoints x ncoeffs up to its square) run on the host in the
+ * same O(n^2) formulation; 0 sends every call to the device.
+ * ------------------------------------------------------------------------- */
+int zk_poly_evaluate(zk_ctx* ctx, zk_field field, zk_repr repr, const zk_fe* coeffs, uint64_t ncoeffs, const zk_fe* xs,
+                     uint64_t npoints, zk_fe* out /* npoints */);
+int zk_dev_poly_evaluate(zk_ctx* ctx, zk_field field, const void* coeffs_tbl, uint64_t ncoeffs, const void* xs_tbl,
+                         uint64_t npoints, void* out_tbl);
+int zk_poly_eval_plan(const zk_ctx* ctx, uint64_t ncoeffs, uint64_t npoints, uint32_t* out_chunks, uint64_t* out_chunk_len);
+int zk_poly_interpolate(zk_ctx* ctx, zk_field field, zk_repr repr, const zk_fe* xs, const zk_fe* ys, uint64_t n,
+                        zk_fe* out_coeffs, uint64_t cap, uint64_t* out_ncoeffs);
+
+/* ---------------------------------------------------------------------------
  * Multi-GPU: the hypercube is split over `world` ranks (one process or thread
  * per GPU, world a power of two). Rank g holds the sub-cube whose LOW
  * log2(world) index bits equal g: local m <-> global m*world + g. The first

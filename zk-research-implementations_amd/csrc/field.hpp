@@ -198,6 +198,39 @@ ZK_HD Fe fe_mul(const Fe& a, const Fe& b) {
   return fe_reduce_once<F>(r);
 }
 
+// x^-1 by Fermat, x^(p - 2): 255 squarings and one product per set bit of
+// p - 2, the same exponent in every lane (no divergence). 0 maps to 0; callers
+// that must tell (the interpolation weights, poly.hpp) test for 0 first.
+template <class F>
+constexpr uint32_t p_minus_2_word(int k) {  // word k of p - 2 (p odd, p > 2)
+  uint32_t borrow = 2, w = 0;
+  for (int i = 0; i <= k; ++i) {
+    w = F::P[i] - borrow;
+    borrow = F::P[i] < borrow ? 1u : 0u;
+  }
+  return w;
+}
+template <class F>
+struct PMinus2 {
+  static constexpr uint32_t W[8] = {p_minus_2_word<F>(0), p_minus_2_word<F>(1), p_minus_2_word<F>(2),
+                                    p_minus_2_word<F>(3), p_minus_2_word<F>(4), p_minus_2_word<F>(5),
+                                    p_minus_2_word<F>(6), p_minus_2_word<F>(7)};
+};
+template <class F>
+ZK_HD Fe fe_inv(const Fe& x) {
+  Fe r = fe_one<F>();
+#pragma unroll
+  for (int w = 7; w >= 0; --w) {  // (unrolled: each word of the exponent is an immediate)
+    const uint32_t e = PMinus2<F>::W[w];
+#pragma unroll 1
+    for (int b = 31; b >= 0; --b) {
+      r = fe_mul<F>(r, r);
+      if ((e >> b) & 1u) r = fe_mul<F>(r, x);
+    }
+  }
+  return r;
+}
+
 // ---- unreduced products (lazy reduction) ------------------------------------
 // Sums of products of Montgomery images are accumulated as 544-bit integers
 // (17 words) and reduced once: REDC is linear, so

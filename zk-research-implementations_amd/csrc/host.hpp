@@ -26,6 +26,7 @@
 #include "gkr_plan.hpp"
 #include "gkr_rounds.hpp"
 #include "fft_plan.hpp"
+#include "poly_plan.hpp"
 
 using zk::Fe;
 
@@ -245,6 +246,12 @@ struct zk_ctx {
   uint32_t fft_stages = kFftTileLog;
   DevBuf fft_scratch[2];
   std::vector<std::unique_ptr<FftTables>> fft_tables;
+  // univariate polynomials (poly.hip): at most this many points run on the host
+  // (ZK_POLY_HOST_MAX; 0: everything on the device); the tree's two ping-pong
+  // levels (M and N, 2 n elements each) and the weight parts / evaluation
+  // cells, all grow-only
+  uint32_t poly_host_max = kPolyHostMaxDefault;
+  DevBuf poly_scratch[3];
   // (the 20-bit signed-window table, 654 MB, is cached per device for the process: kzg.hip FixedBaseCache)
 };
 

@@ -57,6 +57,7 @@ int zk_ctx_create(int device, zk_ctx** out) {
     if (const char* e = getenv("ZK_DTAIL_MAX_QUADS")) c->dtail_max_quads = strtoull(e, nullptr, 0);
     if (const char* e = getenv("ZK_GRID_CAP")) c->grid_cap = (uint32_t)strtoul(e, nullptr, 0);
     if (const char* e = getenv("ZK_FFT_STAGES")) c->fft_stages = fft_stage_cap(strtol(e, nullptr, 0));
+    if (const char* e = getenv("ZK_POLY_HOST_MAX")) c->poly_host_max = poly_host_max(*e ? strtol(e, nullptr, 0) : -1);
     if (const char* e = getenv("ZK_ATOMIC_FANIN")) c->atomic_fanin = (uint32_t)strtoul(e, nullptr, 0);
     if (const char* e = getenv("ZK_DTAIL_BLOCKS")) c->dtail_blocks = (uint32_t)strtoul(e, nullptr, 0);
     if (const char* e = getenv("ZK_GATHER_VARS")) c->gather_vars = (uint32_t)strtoul(e, nullptr, 0);
@@ -120,6 +121,7 @@ void zk_ctx_destroy(zk_ctx* c) {
   c->g1_table.release();
   c->g1_table16.release();
   for (auto& b : c->fft_scratch) b.release();
+  for (auto& b : c->poly_scratch) b.release();
   for (auto& t : c->fft_tables) {
     t->stage_roots.release();
     t->hi.release();

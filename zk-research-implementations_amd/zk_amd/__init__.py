@@ -7,6 +7,8 @@ Python mirror of the reference crates' API (obah/zk-research-implementations):
   sum_check::sum_check_protocol::{prove, verify, gkr_prove, gkr_verify, Proof, GkrProof, GkrVerify}
   merkle_tree::{MerkleTree, MerkleProof, ProofData, LeafSide}  (zk_amd.merkle)
   fft::{fft_evaluate, fft_interpolate, split_poly, get_interpolation_roots}  (zk_amd.fft)
+  univariate_polynomial::UnivariatePoly::{interpolate, evaluate} over many points  (zk_amd.poly)
+  shamir_secret_sharing::{create_polynomia, recover_polynomial, get_secret, share_points}  (zk_amd.shamir)
 over the C ABI of include/zk_sumcheck.h. Every table-sized operation runs in
 the HIP library on a gfx950 GPU; this module only marshals arguments.
 
@@ -50,4 +52,6 @@ from .fft import (  # noqa: F401
     poly_mul,
     split_poly,
 )
+from . import poly  # noqa: F401  (interpolation and batch evaluation over arbitrary points)
+from . import shamir  # noqa: F401  (shamir_secret_sharing crate mirror)
 from ._lib import ZkError  # noqa: F401

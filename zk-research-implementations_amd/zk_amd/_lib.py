@@ -126,6 +126,10 @@ SIGNATURES = {
     "zk_fft_interpolate": (I, [P, I, I, P, U64, P]),
     "zk_dev_fft": (I, [P, I, P, U64, I, P]),
     "zk_poly_mul": (I, [P, I, I, P, U64, P, U64, P, U64, C.POINTER(U64)]),
+    "zk_poly_evaluate": (I, [P, I, I, P, U64, P, U64, P]),
+    "zk_dev_poly_evaluate": (I, [P, I, P, U64, P, U64, P]),
+    "zk_poly_eval_plan": (I, [P, U64, U64, C.POINTER(U32), C.POINTER(U64)]),
+    "zk_poly_interpolate": (I, [P, I, I, P, P, U64, P, U64, C.POINTER(U64)]),
     "zk_ctx_attach_host_comm": (I, [P, I, I, ALLREDUCE_FN, P]),
     "zk_comm_get_unique_id": (I, [P]),
     "zk_ctx_attach_rccl": (I, [P, I, I, P]),

@@ -333,6 +333,20 @@ class UnivariatePoly:
         other.degree()
         return poly_mul(self, other)
 
+    def evaluate_many(self, xs, ctx: Context | None = None) -> list[int]:
+        """evaluate :20-26 at every x of `xs` in one library call (zk_amd.poly)."""
+        from .poly import evaluate_many
+
+        return evaluate_many(self.coefficient, xs, self.field, ctx)
+
+    @staticmethod
+    def interpolate(points, field: int = Field.BN254_FR, ctx: Context | None = None) -> "UnivariatePoly":
+        """interpolate :48-74 through the (x, y) pairs of `points`, trimmed; two
+        points with the same x raise ValueError (zk_amd.poly)."""
+        from .poly import interpolate
+
+        return interpolate(points, field, ctx)
+
 
 # ---------------------------------------------------------------------------
 # sum_check
