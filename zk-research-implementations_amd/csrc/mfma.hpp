@@ -145,7 +145,9 @@ __device__ __forceinline__ void flush_tiles(const i32x16 (&acc)[N], uint32_t cat
 // congruent), normalised to 17 non-negative 32-bit words — the unreduced
 // 17-word product sum of the VALU kernels — and grid_finish.
 // Bounds: |C| <= 2^19 per chunk, so a wave takes at most kD0MChunksMax
-// chunks (int32 tiles); |G| < 2 * 2^16 * 2^510 < M < 2^530 for a block.
+// chunks (int32 tiles); a block then sums 4 x kD0MChunksMax x 32 = 2^18 products per
+// category, each below (2p)^2 < 2^510: |G| < 2^528 < M < 2^530
+// (tests/test_extreme_tables_cpu.py audits these bounds in exact integers).
 // ---------------------------------------------------------------------------
 constexpr uint32_t kD0MChunksMax = 2048;  // chunks of 32 quads per wave (int32 tile bound: 1 MFMA per chunk)
 static_assert(1ull * (1u << 19) * kD0MChunksMax <= (1ull << 30), "d0m tile bound");
@@ -448,7 +450,7 @@ __device__ __forceinline__ Fe dm_finish(const int64_t (&W)[8], const Fe& x00) {
     y[7] = (uint32_t)tt;
     top = tt >> 32;
   }
-  // V = y + top 2^256 in (-2^208, p + 2^208); x00 + V + p in (0, 3p + 2^208): two conditional subtractions
+  // V = y + top 2^256 in (-2^207, p + p / 2^32 + 2^207); x00 + V + p in (0, 4p): two conditional subtractions
   Fe s;
   uint32_t c1 = 0, c2 = 0;
 #pragma unroll
@@ -835,7 +837,8 @@ __global__ __launch_bounds__(kBlock, 2) void k_gkr_d0t(const Fe* __restrict__ A,
 // (partial_evaluate three times, multilinear_polynomial_evaluation.rs:52-63), as ONE
 // K = 256 MFMA product per 32 elements: A = digits of w_c[k] = eq(r, c)
 // 2^(8k + 64) mod p, B = the inputs' own digits (every input is < p: no
-// differences, no lazy ranges). Then the eight grid-point products of
+// differences, no lazy ranges; position sums <= 256 x 2^14 = 2^22, still
+// |Y| < 2^271 for dm_finish). Then the eight grid-point products of
 // rounds i, i+1 over level i's quads, exactly as k_gkr_dm.
 // ---------------------------------------------------------------------------
 struct DM3Scratch : DMScratch {
