@@ -219,6 +219,71 @@ int zk_gkr_circuit_verify(zk_field field, zk_repr repr, uint32_t nlayers, const 
                           const uint8_t* ncoeffs, const zk_fe* claims, const zk_fe* input_evals, int* out_verified);
 
 /* ---------------------------------------------------------------------------
+ * GKR over a circuit with explicit wiring: the protocol above
+ * (gkr_protocol.rs:31-126) for any layered circuit, not only the binary tree.
+ * Layers are given input -> output: gates[l] >= 1 gates in layer l; ops, left
+ * and right are concatenated layer by layer; gate g of layer l computes
+ * in[left_g] op in[right_g] (0 = Add, 1 = Mul) over the n_below(l) values of
+ * the layer below (n_below(0) = ninputs >= 1, else gates[l-1]). Counts need
+ * not be powers of two, left == right is allowed, wires may be shared or
+ * unused, a layer may be wider than the one below.
+ *   kb(l) = max(1, ceil log2 n_below(l)), ka(l) = max(1, ceil log2 gates[l]).
+ * A layer's value table is its inputs zero-padded to 2^kb(l); the wiring
+ * predicates are zero on padding. The output polynomial is the last layer's
+ * values zero-padded to 2^v, v = ka(nlayers-1): all 2^v values are absorbed,
+ * v challenges r0 are drawn one after the other, m0 = MLE(out)(r0) (MSB
+ * first) is absorbed. Layer l's sum-check (output layer first) has 2 kb(l)
+ * rounds, the bits of b then those of c, over
+ *   f(b,c) = sum_{g: left_g=b, right_g=c} wt_g (op_g = Add ? w(b)+w(c) : w(b) w(c)),
+ * wt_g = eq(r0, g) for the output layer, alpha eq(r_b', g) + beta eq(r_c', g)
+ * below it (r_b', r_c' the halves of the previous layer's challenges). After
+ * every layer but the input layer o1 = w(r_b) is absorbed, alpha drawn,
+ * o2 = w(r_c) absorbed, beta drawn. A tree-shaped wired circuit (left = 2g,
+ * right = 2g+1, halving powers of two, ninputs = 2 gates[0]) gives the bytes
+ * zk_gkr_circuit_prove gives.
+ * ZK_EINVAL: a null array, nlayers = 0, ninputs = 0, a layer without gates, an
+ * op > 1, a wire index >= n_below. ZK_EUNSUPPORTED: more than 256 layers, a
+ * gates[l] or ninputs above 2^24, more than 2^26 gates in all. The largest
+ * shape tested is 2^20 inputs feeding a 2^20-gate layer; between that and the
+ * 2^24 cap nothing has been run or measured.
+ *   zk_gkr_wired_new    validates and keeps the circuit with its context: the
+ *                       wiring and its two groupings per layer (gates by left
+ *                       input, gates by right input) live on the device.
+ *   zk_gkr_wired_free   releases it (NULL is a no-op). Circuits still alive
+ *                       when their context is destroyed are released with it
+ *                       and must not be freed afterwards.
+ *   zk_gkr_wired_shape  (host only) total rounds = sum of 2 kb(l), and v.
+ *   zk_gkr_wired_prove  on the circuit's context. Outputs (rounds in processing
+ *                       order, output layer first): out_output_poly[2^v],
+ *                       out_coeffs[3*total] + out_ncoeffs[total] (trimmed),
+ *                       out_challenges[total], out_claims[2*(nlayers-1)],
+ *                       out_input_evals[2] = the input MLE at the last layer's
+ *                       (r_b, r_c), which compose with zk_kzg_* as the tree
+ *                       prover's do. Nothing is written on failure.
+ *                       Layers with kb(l) <= ZK_CIRCUIT_HOST_LGL run on the
+ *                       host; ZK_CIRCUIT_DENSE does not apply.
+ *   zk_gkr_wired_verify (host only, no ctx) the verifier: the wiring extension
+ *                       at a layer's point is sum_g wt_g eq(r_b, left_g)
+ *                       eq(r_c, right_g) per op, from eq tables in O(gates +
+ *                       2^k). inputs may be NULL (the input evaluations are
+ *                       then not re-derived). A rejected proof is ZK_OK with
+ *                       *out_verified = 0.
+ * ------------------------------------------------------------------------- */
+typedef struct zk_wired_circuit zk_wired_circuit;
+int zk_gkr_wired_new(zk_ctx* ctx, uint32_t nlayers, const uint32_t* gates, const uint8_t* ops, const uint32_t* left,
+                     const uint32_t* right, uint32_t ninputs, zk_wired_circuit** out);
+void zk_gkr_wired_free(zk_wired_circuit* circuit);
+int zk_gkr_wired_shape(uint32_t nlayers, const uint32_t* gates, uint32_t ninputs, uint32_t* out_total_rounds,
+                       uint32_t* out_output_vars);
+int zk_gkr_wired_prove(zk_wired_circuit* circuit, zk_field field, zk_repr repr, const zk_fe* inputs,
+                       zk_fe* out_output_poly, zk_fe* out_coeffs, uint8_t* out_ncoeffs, zk_fe* out_challenges,
+                       zk_fe* out_claims, zk_fe* out_input_evals);
+int zk_gkr_wired_verify(zk_field field, zk_repr repr, uint32_t nlayers, const uint32_t* gates, const uint8_t* ops,
+                        const uint32_t* left, const uint32_t* right, uint32_t ninputs, const zk_fe* inputs,
+                        const zk_fe* output_poly, const zk_fe* coeffs, const uint8_t* ncoeffs, const zk_fe* claims,
+                        const zk_fe* input_evals, int* out_verified);
+
+/* ---------------------------------------------------------------------------
  * Multilinear KZG over BLS12-381 G1 (pcs/src/kzg_pcs/kzg.rs).
  * Scalars are BLS12-381 Fr (zk_fe, repr as elsewhere). Points are affine with
  * canonical little-endian 48-byte coordinates; (0, 0) is the point at infinity.

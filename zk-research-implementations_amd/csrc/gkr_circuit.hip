@@ -127,33 +127,8 @@ void gkr_layer_two_phase(zk_ctx* c, const Fe* w, const Fe* wt, const uint8_t* op
 // reference's own arithmetic: gkr_prove (sum_check_protocol.rs:86-115) with
 // get_round_partial_polynomial_proof_gkr (:152-166) and partial_evaluate
 // (multilinear_polynomial_evaluation.rs:52-63); each round's three values are
-// summed unreduced and reduced once.
-template <class F>
-void host_layer_phase(std::vector<Fe> (&T)[4], uint32_t n, uint32_t k0, zk_transcript* tr, GkrOut& out) {
-  Fe r;
-  for (uint32_t i = 0; i < n; ++i) {
-    Fe e0, e1, e2;
-    host_round_sums<F, true>(T, e0, e2, &e1);
-    finish_round<F>(tr, e0, e1, e2, k0 + i, out, r);
-    host_fold<F>(T, r);  // (after the last round: the tables at the phase's point, one entry each)
-  }
-}
-// eq(pt, v) for every v < 2^n, bit n-1-k of v against pt[k] (MSB first):
-// one product per entry (the table doubles once per coordinate)
-template <class F>
-std::vector<Fe> host_eq_table(const Fe* pt, uint32_t n) {
-  std::vector<Fe> t(1, zk::fe_one<F>());
-  for (uint32_t k = 0; k < n; ++k) {
-    std::vector<Fe> u(2 * t.size());
-    for (size_t j = 0; j < t.size(); ++j) {
-      const Fe x = zk::hfe_mul<F>(t[j], pt[k]);
-      u[2 * j] = zk::hfe_sub<F>(t[j], x);
-      u[2 * j + 1] = x;
-    }
-    t.swap(u);
-  }
-  return t;
-}
+// summed unreduced and reduced once (host_layer_phase and host_eq_table,
+// gkr_rounds.hpp).
 // w = the layer's L inputs, wt = its G gate weights (k_gate_weights), ops its gate ops
 // (ev = {w(r_b), w(r_c)} from the folds, as in gkr_layer_two_phase)
 template <class F>
@@ -383,16 +358,6 @@ Fe eq_bits(const Fe* pt, uint64_t v, uint32_t n) {
     e = zk::fe_mul<F>(e, bit ? pt[k] : zk::fe_sub<F>(zk::fe_one<F>(), pt[k]));
   }
   return e;
-}
-
-template <class F>
-Fe mle_eval_host(std::vector<Fe> t, const std::vector<Fe>& pt) {  // MultilinearPoly::evaluate (:79-91)
-  for (const Fe& r : pt) {
-    const size_t h = t.size() / 2;
-    for (size_t j = 0; j < h; ++j) t[j] = zk::fe_add<F>(t[j], zk::fe_mul<F>(r, zk::fe_sub<F>(t[j + h], t[j])));
-    t.resize(h);
-  }
-  return t[0];
 }
 
 // gkr::verify (gkr_protocol.rs:128-227). The wiring MLEs are evaluated

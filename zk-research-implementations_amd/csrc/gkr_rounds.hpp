@@ -126,6 +126,45 @@ void host_round_sums(const std::vector<Fe> (&T)[4], Fe& e0, Fe& e2, Fe* e1 = nul
   e2 = wide_to_fe<F>(a2);
 }
 
+// One phase of a circuit layer's sum-check entirely on the host (the tree
+// prover's host_layer in gkr_circuit.hip, the wired prover's in wired.hip): n
+// rounds over the four tables T, starting at global round k0.
+template <class F>
+void host_layer_phase(std::vector<Fe> (&T)[4], uint32_t n, uint32_t k0, zk_transcript* tr, GkrOut& out) {
+  Fe r;
+  for (uint32_t i = 0; i < n; ++i) {
+    Fe e0, e1, e2;
+    host_round_sums<F, true>(T, e0, e2, &e1);
+    finish_round<F>(tr, e0, e1, e2, k0 + i, out, r);
+    host_fold<F>(T, r);  // (after the last round: the tables at the phase's point, one entry each)
+  }
+}
+// eq(pt, v) for every v < 2^n, bit n-1-k of v against pt[k] (MSB first):
+// one product per entry (the table doubles once per coordinate)
+template <class F>
+std::vector<Fe> host_eq_table(const Fe* pt, uint32_t n) {
+  std::vector<Fe> t(1, zk::fe_one<F>());
+  for (uint32_t k = 0; k < n; ++k) {
+    std::vector<Fe> u(2 * t.size());
+    for (size_t j = 0; j < t.size(); ++j) {
+      const Fe x = zk::hfe_mul<F>(t[j], pt[k]);
+      u[2 * j] = zk::hfe_sub<F>(t[j], x);
+      u[2 * j + 1] = x;
+    }
+    t.swap(u);
+  }
+  return t;
+}
+template <class F>
+Fe mle_eval_host(std::vector<Fe> t, const std::vector<Fe>& pt) {  // MultilinearPoly::evaluate (:79-91)
+  for (const Fe& r : pt) {
+    const size_t h = t.size() / 2;
+    for (size_t j = 0; j < h; ++j) t[j] = zk::hfe_add<F>(t[j], zk::hfe_mul<F>(r, zk::hfe_sub<F>(t[j + h], t[j])));
+    t.resize(h);
+  }
+  return t[0];
+}
+
 // The four tables folded by every challenge of a phase (the multilinear
 // extensions at the phase's point), when its last rounds ran on the host.
 struct FinalVals {

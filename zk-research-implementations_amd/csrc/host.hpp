@@ -252,6 +252,8 @@ struct zk_ctx {
   // cells, all grow-only
   uint32_t poly_host_max = kPolyHostMaxDefault;
   DevBuf poly_scratch[3];
+  // wired GKR circuits (wired.hip) made on this context and not yet freed: they die with it
+  std::vector<zk_wired_circuit*> wired;
   // (the 20-bit signed-window table, 654 MB, is cached per device for the process: kzg.hip FixedBaseCache)
 };
 
@@ -283,6 +285,7 @@ inline zk::RPost* d_rpost(zk_ctx* c) { return reinterpret_cast<zk::RPost*>(reint
 static_assert(6656 + sizeof(zk::RPost) <= 8192 && 6144 + sizeof(zk::RPost) <= kHostPage, "relay slot overlaps");
 
 inline void bind(zk_ctx* c) { HIPCK(hipSetDevice(c->device)); }
+void wired_release_all(zk_ctx* c);  // wired.hip: frees c->wired (zk_ctx_destroy)
 
 // At most one resident wave of 256-thread blocks (blocks/CU from the
 // kernel's register budget), grid-striding over the rest: no tail of

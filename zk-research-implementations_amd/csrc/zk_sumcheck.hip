@@ -102,6 +102,7 @@ void zk_ctx_destroy(zk_ctx* c) {
   (void)hipSetDevice(c->device);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   if (c->nccl) (void)ncclCommDestroy(c->nccl);
+  wired_release_all(c);
   for (auto& p : c->pending) c->ev_free.push_back({p.a, p.b});
   for (auto& e : c->ev_free) {
     (void)hipEventDestroy(e.first);

@@ -39,7 +39,7 @@ from .api import (  # noqa: F401
     verify,
 )
 from .context import Context, DeviceTable  # noqa: F401
-from . import gkr  # noqa: F401  (gkr crate mirror: Circuit, Operation, prove, verify)
+from . import gkr  # noqa: F401  (gkr crate mirror: Circuit, WiredCircuit, Operation, prove, verify)
 from . import merkle  # noqa: F401  (merkle_tree crate mirror)
 from .merkle import LeafSide, MerkleProof, MerkleTree, ProofData  # noqa: F401
 from . import fft  # noqa: F401  (fft crate mirror, polynomial product)

@@ -81,6 +81,11 @@ SIGNATURES = {
     "zk_gkr_circuit_verify": (I, [I, I, U32, P, P, P, U32, P, P, P, P, P, C.POINTER(C.c_int)]),
     "zk_gkr_circuit_prove_kzg": (I, [P, I, U32, P, P, P, U32, P, P, P, P, P, P, P, P, P, P]),
     "zk_gkr_circuit_verify_kzg": (I, [I, U32, P, P, P, P, P, P, P, P, P, P, C.POINTER(C.c_int)]),
+    "zk_gkr_wired_new": (I, [P, U32, P, P, P, P, U32, C.POINTER(C.c_void_p)]),
+    "zk_gkr_wired_free": (None, [P]),
+    "zk_gkr_wired_shape": (I, [U32, P, U32, C.POINTER(U32), C.POINTER(U32)]),
+    "zk_gkr_wired_prove": (I, [P, I, I, P, P, P, P, P, P, P]),
+    "zk_gkr_wired_verify": (I, [I, I, U32, P, P, P, P, U32, P, P, P, P, P, P, C.POINTER(C.c_int)]),
     "zk_kzg_setup": (I, [P, I, P, U32, C.POINTER(C.c_void_p)]),
     "zk_kzg_free": (None, [P]),
     "zk_kzg_lagrange_basis": (I, [P, P, U32, P]),
