@@ -284,6 +284,67 @@ int zk_gkr_wired_verify(zk_field field, zk_repr repr, uint32_t nlayers, const ui
                         const zk_fe* input_evals, int* out_verified);
 
 /* ---------------------------------------------------------------------------
+ * Sum-check over any sum of products of multilinear tables:
+ * gkr_prove's loop (sum_check_protocol.rs:86-166) with SumPoly::reduce done in
+ * full, beside zk_gkr_sumcheck_prove, which keeps the reference's four-table
+ * reduce and its bytes. Given ntables distinct tables of 2^nvars elements and
+ * nterms products of `degree` factors, each factor an index into the tables
+ * (factors[t * degree + d], term-major; an index may repeat within a term and
+ * across terms), the polynomial is f = sum_t prod_d table[factors[t][d]].
+ * Round k: y_i = sum_j f_k(i, j) for i = 0..degree, variable 0 (the MSB) bound
+ * to i as partial_evaluate(0, i) binds it; the polynomial of degree <= degree
+ * through (i, y_i), trailing zeros trimmed; its coefficient bytes absorbed
+ * (none when it trims to nothing); one challenge r_k; every table folded by
+ * r_k. With ntables = 4 and factors = {0,1, 2,3} the outputs are
+ * zk_gkr_sumcheck_prove's, byte for byte. claimed_sum is carried through and
+ * influences no round polynomial.
+ * Caps: ntables <= 16, nterms <= 16, nvars <= 26, and */
+#define ZK_COMPOSED_MAX_DEGREE 4 /* degree <= 4: the highest whose round kernels were built and found free of scratch */
+/* ZK_EINVAL: a null pointer, ntables, nterms or degree = 0, a factor index >=
+ * ntables, an unknown field or repr, a value >= p. ZK_EUNSUPPORTED: a cap
+ * exceeded. nvars = 0 is valid: no rounds, out_table_evals are the single
+ * entries (out_coeffs, out_ncoeffs and out_challenges may then be NULL).
+ * Nothing is written on failure.
+ *   zk_composed_sumcheck_prove      tables in host memory. Outputs:
+ *                       out_coeffs[(degree+1)*nvars] (round k at (degree+1)*k,
+ *                       zero past its trimmed count out_ncoeffs[k]),
+ *                       out_challenges[nvars], out_table_evals[ntables] = table
+ *                       i at the challenge point (the fully folded table: the
+ *                       verifier's final check is final_claim ==
+ *                       combine(table_evals)), *out_claimed_sum = claimed_sum.
+ *                       Rounds whose tables have at most 2^ZK_COMPOSED_HOST_LG
+ *                       entries (default 6, read at zk_ctx_create; 0: every
+ *                       round on the device) run on the host.
+ *   zk_dev_composed_sumcheck_prove  the same over Montgomery tables already in
+ *                       device memory (repr: the scalars in and out). The
+ *                       inputs are only read; the folds live in the context's
+ *                       workspace.
+ *   zk_composed_sumcheck_verify     (host only, no ctx) gkr_verify with a
+ *                       degree bound over coeffs[(degree+1)*nrounds]. A round
+ *                       with ncoeffs[k] > degree + 1, or with s(0) + s(1) !=
+ *                       claim, is ZK_OK with *out_verified = 0, final claim 0
+ *                       and one zero challenge, as zk_gkr_sumcheck_verify.
+ *   zk_composed_combine             (host only) sum_t prod_d
+ *                       table_evals[factors[t][d]].
+ * ------------------------------------------------------------------------- */
+int zk_composed_sumcheck_prove(zk_ctx* ctx, zk_field field, zk_repr repr, const zk_fe* const* tables, uint32_t ntables,
+                               uint32_t nvars, const uint8_t* factors, uint32_t nterms, uint32_t degree,
+                               const zk_fe* claimed_sum, zk_transcript* transcript, zk_fe* out_coeffs,
+                               uint8_t* out_ncoeffs, zk_fe* out_challenges, zk_fe* out_table_evals,
+                               zk_fe* out_claimed_sum);
+int zk_dev_composed_sumcheck_prove(zk_ctx* ctx, zk_field field, zk_repr repr, const void* const* d_tables,
+                                   uint32_t ntables, uint32_t nvars, const uint8_t* factors, uint32_t nterms,
+                                   uint32_t degree, const zk_fe* claimed_sum, zk_transcript* transcript,
+                                   zk_fe* out_coeffs, uint8_t* out_ncoeffs, zk_fe* out_challenges,
+                                   zk_fe* out_table_evals, zk_fe* out_claimed_sum);
+int zk_composed_sumcheck_verify(zk_field field, zk_repr repr, uint32_t degree, const zk_fe* coeffs,
+                                const uint8_t* ncoeffs, uint32_t nrounds, const zk_fe* claimed_sum,
+                                zk_transcript* transcript, int* out_verified, zk_fe* out_final_claim,
+                                zk_fe* out_challenges);
+int zk_composed_combine(zk_field field, zk_repr repr, const zk_fe* table_evals, uint32_t ntables,
+                        const uint8_t* factors, uint32_t nterms, uint32_t degree, zk_fe* out);
+
+/* ---------------------------------------------------------------------------
  * Multilinear KZG over BLS12-381 G1 (pcs/src/kzg_pcs/kzg.rs).
  * Scalars are BLS12-381 Fr (zk_fe, repr as elsewhere). Points are affine with
  * canonical little-endian 48-byte coordinates; (0, 0) is the point at infinity.

@@ -27,6 +27,7 @@
 #include "gkr_rounds.hpp"
 #include "fft_plan.hpp"
 #include "poly_plan.hpp"
+#include "composed_plan.hpp"
 
 using zk::Fe;
 
@@ -252,6 +253,9 @@ struct zk_ctx {
   // cells, all grow-only
   uint32_t poly_host_max = kPolyHostMaxDefault;
   DevBuf poly_scratch[3];
+  // composed sum-check (composed.hip): rounds whose tables have at most 2^this entries run on the host
+  // (ZK_COMPOSED_HOST_LG; 0: every round on the device)
+  uint32_t composed_host_lg = zkc::kComposedHostLgDefault;
   // wired GKR circuits (wired.hip) made on this context and not yet freed: they die with it
   std::vector<zk_wired_circuit*> wired;
   // (the 20-bit signed-window table, 654 MB, is cached per device for the process: kzg.hip FixedBaseCache)

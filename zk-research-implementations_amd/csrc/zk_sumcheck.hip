@@ -69,6 +69,8 @@ int zk_ctx_create(int device, zk_ctx** out) {
     if (const char* e = getenv("ZK_MALL_ORDER")) c->mall_order = std::min<uint32_t>((uint32_t)strtoul(e, nullptr, 0), 2u);
     if (const char* e = getenv("ZK_HOST_ROUNDS"))  // (<= 8: the tail hands over 4 x 2^(H+2) elements)
       c->host_rounds = std::min<uint32_t>((uint32_t)strtoul(e, nullptr, 0), 8u);
+    if (const char* e = getenv("ZK_COMPOSED_HOST_LG"))
+      c->composed_host_lg = std::min<uint32_t>((uint32_t)strtoul(e, nullptr, 0), zkc::kComposedHostLgMax);
     if (const char* e = getenv("ZK_DEVICE_FS")) c->device_fs = atoi(e) != 0;
     if (const char* e = getenv("ZK_TAIL_MAX_PAIRS")) c->tail_max_pairs = strtoull(e, nullptr, 0);
     c->num_cus = prop.multiProcessorCount;

@@ -5,6 +5,7 @@ Python mirror of the reference crates' API (obah/zk-research-implementations):
   multilinear_polynomial::{MultilinearPoly, ProductPoly, SumPoly}
   univariate_polynomial::UnivariatePoly
   sum_check::sum_check_protocol::{prove, verify, gkr_prove, gkr_verify, Proof, GkrProof, GkrVerify}
+  gkr_prove / gkr_verify over every product and factor of a SumPoly: composed_prove, composed_verify, composed_combine
   merkle_tree::{MerkleTree, MerkleProof, ProofData, LeafSide}  (zk_amd.merkle)
   fft::{fft_evaluate, fft_interpolate, split_poly, get_interpolation_roots}  (zk_amd.fft)
   univariate_polynomial::UnivariatePoly::{interpolate, evaluate} over many points  (zk_amd.poly)
@@ -18,6 +19,7 @@ Field elements are canonical Python ints, or numpy uint64 arrays of shape
 from __future__ import annotations
 
 from .api import (  # noqa: F401
+    ComposedProof,
     Field,
     GkrProof,
     GkrVerify,
@@ -28,6 +30,9 @@ from .api import (  # noqa: F401
     Transcript,
     UnivariatePoly,
     blob_info,
+    composed_combine,
+    composed_prove,
+    composed_verify,
     default_context,
     fq_vec_to_bytes,
     gkr_prove,

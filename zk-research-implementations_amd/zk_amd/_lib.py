@@ -86,6 +86,10 @@ SIGNATURES = {
     "zk_gkr_wired_shape": (I, [U32, P, U32, C.POINTER(U32), C.POINTER(U32)]),
     "zk_gkr_wired_prove": (I, [P, I, I, P, P, P, P, P, P, P]),
     "zk_gkr_wired_verify": (I, [I, I, U32, P, P, P, P, U32, P, P, P, P, P, P, C.POINTER(C.c_int)]),
+    "zk_composed_sumcheck_prove": (I, [P, I, I, P, U32, U32, P, U32, U32, P, P, P, P, P, P, P]),
+    "zk_dev_composed_sumcheck_prove": (I, [P, I, I, P, U32, U32, P, U32, U32, P, P, P, P, P, P, P]),
+    "zk_composed_sumcheck_verify": (I, [I, I, U32, P, P, U32, P, P, C.POINTER(C.c_int), P, P]),
+    "zk_composed_combine": (I, [I, I, P, U32, P, U32, U32, P]),
     "zk_kzg_setup": (I, [P, I, P, U32, C.POINTER(C.c_void_p)]),
     "zk_kzg_free": (None, [P]),
     "zk_kzg_lagrange_basis": (I, [P, P, U32, P]),

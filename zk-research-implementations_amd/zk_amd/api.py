@@ -225,6 +225,25 @@ class ProductPoly:
         self.evaluation = [MultilinearPoly(e, field, ctx) for e in evs]
         self.field = Field(field)
 
+    @classmethod
+    def from_polys(cls, polys: list[MultilinearPoly]) -> "ProductPoly":
+        """A product of existing MultilinearPoly objects (kept, not copied), so that
+        several products, or several factors of one, can share a table:
+        SumPoly.composed_tables() tells tables apart by object identity."""
+        polys = list(polys)
+        if not polys:
+            raise ValueError("index out of bounds: evaluations[0]")
+        if any(not isinstance(m, MultilinearPoly) for m in polys):
+            raise ValueError("from_polys takes MultilinearPoly objects")
+        if any(m.limbs.shape[0] != polys[0].limbs.shape[0] for m in polys):
+            raise ValueError("all evaluations must have same length")
+        if any(m.field != polys[0].field for m in polys):
+            raise ValueError("the factors are over different fields")
+        self = cls.__new__(cls)
+        self.evaluation = polys
+        self.field = polys[0].field
+        return self
+
     def get_degree(self) -> int:  # :56-58
         return len(self.evaluation)
 
@@ -283,6 +302,26 @@ class SumPoly:
                     # the reference zips (truncates) or panics once a smaller table is exhausted
                     raise ValueError("all tables of a SumPoly must have the same length")
         return [m.limbs for m in t]
+
+
+    def composed_tables(self) -> tuple[list[np.ndarray], list[list[int]]]:
+        """(tables, factors) for composed_prove: the distinct tables over all
+        products and all factors, deduplicated by object identity in order of
+        first mention, and per product the indices of its factors."""
+        tables: list[np.ndarray] = []
+        index: dict[int, int] = {}
+        factors = []
+        for pp in self.polys:
+            row = []
+            for mle in pp.evaluation:
+                if id(mle) not in index:
+                    index[id(mle)] = len(tables)
+                    tables.append(mle.limbs)
+                row.append(index[id(mle)])
+            factors.append(row)
+        if any(t.shape[0] != tables[0].shape[0] for t in tables):
+            raise ValueError("all tables of a SumPoly must have the same length")
+        return tables, factors
 
 
 # ---------------------------------------------------------------------------
@@ -506,6 +545,80 @@ def gkr_verify(round_polys: list[UnivariatePoly], claimed_sum: int, transcript: 
     if not ok.value:
         return GkrVerify(False, 0, [0])
     return GkrVerify(True, to_ints(fin)[0], to_ints(ch[:n]))
+
+
+@dataclass
+class ComposedProof:
+    proof_polynomials: list[UnivariatePoly]
+    claimed_sum: int
+    random_challenges: list[int]
+    table_evals: list[int]  # every distinct table at the challenge point (SumPoly.composed_tables order)
+
+
+def _factor_array(factors) -> tuple[np.ndarray, int, int]:
+    rows = [list(r) for r in factors]
+    if not rows or not rows[0] or any(len(r) != len(rows[0]) for r in rows):
+        raise ValueError("factors must be a non-empty list of equally long, non-empty index lists")
+    if any(not 0 <= i < 256 for r in rows for i in r):
+        raise ValueError("a factor names a table >= ntables")
+    return np.array(rows, np.uint8).reshape(-1), len(rows), len(rows[0])
+
+
+def composed_prove(claimed_sum: int, sum_poly: SumPoly, transcript: Transcript,
+                   ctx: Context | None = None) -> ComposedProof:
+    """gkr_prove (:86-115) with SumPoly::reduce done in full: the sum-check of
+    sum_t prod_d of every product and every factor of `sum_poly`, round
+    polynomials of degree get_degree() (zk_composed_sumcheck_prove)."""
+    tables, factors = sum_poly.composed_tables()
+    fac, nterms, degree = _factor_array(factors)
+    ctx = ctx or sum_poly.polys[0].evaluation[0].ctx or default_context()
+    n = tables[0].shape[0].bit_length() - 1
+    arr = (C.c_void_p * len(tables))(*[t.ctypes.data for t in tables])
+    coeffs = np.zeros((max(n, 1), degree + 1, 4), np.uint64)
+    nco = np.zeros(max(n, 1), np.uint8)
+    ch = np.zeros((max(n, 1), 4), np.uint64)
+    ev = np.zeros((len(tables), 4), np.uint64)
+    cs = np.zeros((1, 4), np.uint64)
+    _call(lib().zk_composed_sumcheck_prove(ctx.h, int(sum_poly.field), REPR_CANONICAL, arr, len(tables), n, ptr(fac),
+                                           nterms, degree, ptr(one(claimed_sum)), transcript.h, ptr(coeffs), ptr(nco),
+                                           ptr(ch), ptr(ev), ptr(cs)))
+    polys = [UnivariatePoly(to_ints(coeffs[k, : nco[k]]), sum_poly.field) for k in range(n)]
+    return ComposedProof(polys, to_ints(cs)[0], to_ints(ch[:n]), to_ints(ev))
+
+
+def composed_verify(round_polys: list[UnivariatePoly], claimed_sum: int, transcript: Transcript,
+                    degree: int) -> GkrVerify:
+    """gkr_verify (:117-150) with a degree bound: a round polynomial with more
+    than degree + 1 coefficients is rejected like a failed round check. The
+    caller finishes with final_claimed_sum == composed_combine(table_evals, factors)."""
+    n = len(round_polys)
+    field = transcript.field
+    coeffs = np.zeros((max(n, 1), degree + 1, 4), np.uint64)
+    nco = np.zeros(max(n, 1), np.uint8)
+    for k, rp in enumerate(round_polys):
+        c = rp.coefficient if isinstance(rp, UnivariatePoly) else list(rp)
+        nco[k] = min(len(c), 255)
+        keep = c[: degree + 1]
+        if keep:
+            coeffs[k, : len(keep)] = as_limbs(keep)
+    ok = C.c_int(0)
+    fin = np.zeros((1, 4), np.uint64)
+    ch = np.zeros((max(n, 1), 4), np.uint64)
+    _call(lib().zk_composed_sumcheck_verify(int(field), REPR_CANONICAL, int(degree), ptr(coeffs), ptr(nco), n,
+                                            ptr(one(claimed_sum)), transcript.h, C.byref(ok), ptr(fin), ptr(ch)))
+    if not ok.value:
+        return GkrVerify(False, 0, [0])
+    return GkrVerify(True, to_ints(fin)[0], to_ints(ch[:n]))
+
+
+def composed_combine(table_evals, factors, field: int = Field.BN254_FR) -> int:
+    """sum_t prod_d table_evals[factors[t][d]] (zk_composed_combine)."""
+    fac, nterms, degree = _factor_array(factors)
+    ev = as_limbs(list(table_evals))
+    out = np.zeros((1, 4), np.uint64)
+    _call(lib().zk_composed_combine(int(field), REPR_CANONICAL, ptr(ev), ev.shape[0], ptr(fac), nterms, degree,
+                                    ptr(out)))
+    return to_ints(out)[0]
 
 
 def gkr_verify_blob(blob: bytes, transcript: Transcript) -> GkrVerify:
