@@ -434,6 +434,133 @@ int zk_gkr_circuit_verify_kzg(zk_repr repr, uint32_t nlayers, const uint32_t* ga
                               const zk_g1* proofs, const zk_g2* g2_taus, int* out_verified);
 
 /* ---------------------------------------------------------------------------
+ * Sum-check over KZG-committed tables with one batched opening.
+ * zk_composed_sumcheck_* ends with table_evals[i], table i at the challenge
+ * point; these entry points tie those values to commitments, so that an
+ * identity such as eq (a b - c) = 0 is an argument about committed a, b, c.
+ * BLS12-381 Fr throughout, as all KZG here, except the two table builders,
+ * which take any field.
+ *
+ * Table builders (device tables are Montgomery, as zk_dev_upload leaves them;
+ * repr applies to the host scalars):
+ *   zk_dev_mle_lincomb   d_out[j] = sum_i coeffs[i] table_i[j] + constant
+ *                        (constant NULL = 0) for j < count. 1 <= ntables <= 16,
+ *                        count >= 1; the same table may appear more than once;
+ *                        d_out must be none of the inputs (pointers compared)
+ *                        and must not overlap one. ZK_EINVAL: a null pointer,
+ *                        ntables = 0, count = 0, d_out equal to an input, a
+ *                        coefficient or constant >= p, an unknown field or
+ *                        repr. ZK_EUNSUPPORTED: ntables > 16. Nothing is
+ *                        written on failure.
+ *   zk_dev_mle_eq_table  d_out[j] = eq(point, bits of j) for j < 2^n, bit
+ *                        n-1-k of j against point[k] (MSB first, the order the
+ *                        sum-checks bind variables in). n <= 26
+ *                        (ZK_EUNSUPPORTED above); n = 0 gives the single entry 1.
+ *   zk_mle_eq_table      the same into host memory.
+ *   zk_mle_eq_eval       (host only, no ctx) prod_i (a_i b_i + (1 - a_i)(1 - b_i)):
+ *                        the eq table of a at the point b, what a verifier
+ *                        computes for a public eq table.
+ *
+ * Batched KZG (k tables over one setup, opened at ONE point by one proof, by
+ * the random linear combination with weights rho^0 .. rho^(k-1) in the order
+ * given; 1 <= ntables <= 16, ZK_EUNSUPPORTED above):
+ *   zk_dev_kzg_commit_batch / zk_kzg_commit_batch   out[i] = KZG::commit of
+ *                        table i: one MSM per table.
+ *   zk_dev_kzg_batch_open / zk_kzg_batch_open       get_proof(v, point, g) for
+ *                        g = sum_j rho^j table_j and v = sum_j rho^j
+ *                        opened_values[j]: nvars quotient commitments. One
+ *                        streaming pass over the tables, then the work of one
+ *                        zk_dev_kzg_get_proof; with ntables = 1 its bytes,
+ *                        whatever rho is.
+ *   zk_kzg_batch_verify  (host only, no ctx) KZG::verify of C = sum_j rho^j
+ *                        commitments[j] against the same v. Commitments must be
+ *                        on the curve ((0, 0), infinity, is: an all-zero table
+ *                        commits to it); nproof != npoint is ZK_EINVAL.
+ *
+ * The committed sum-check. Bit i of committed_mask says table i is committed;
+ * the other tables are public (eq, selectors, a table of ones), and the
+ * verifier evaluates those itself. The transcript, on the caller's handle:
+ *   1. for each committed table in index order, append 96 bytes: x then y,
+ *      each canonical little-endian 48 bytes, as zk_g1 holds them (infinity
+ *      is 96 zero bytes);
+ *   2. the composed sum-check, exactly as zk_composed_sumcheck_prove runs it;
+ *   3. append(fq_vec_to_bytes(table_evals[0..ntables))), then rho =
+ *      get_random_challenge;
+ *   4. the j-th committed table (index order) gets rho^j; the opening is
+ *      batch_open at the sum-check's challenges with the committed tables'
+ *      table_evals as opened values (the sum-check binds variable 0, the MSB,
+ *      first, and get_proof divides out the top variable first: the same point).
+ *   zk_committed_sumcheck_prove      tables in host memory (uploaded once, for
+ *                        the sum-check and the opening). Writes everything
+ *                        zk_composed_sumcheck_prove writes, then
+ *                        out_commitments[popcount(mask)] in table-index order
+ *                        and out_opening[nvars]. commitments_in (NULL: compute
+ *                        them) lets a prover reuse commitments made once: they
+ *                        are absorbed and returned as given, not recomputed
+ *                        (only checked to be on the curve).
+ *   zk_dev_committed_sumcheck_prove  the same over Montgomery tables on the
+ *                        device; the inputs are only read.
+ *   zk_committed_sumcheck_verify     (host only, no ctx) *out_verified = 1
+ *                        requires all of: the composed verifier accepts,
+ *                        final_claim == combine(table_evals), and
+ *                        zk_kzg_batch_verify accepts the opening at the
+ *                        verifier's own challenges. A failed check is ZK_OK
+ *                        with *out_verified = 0 and one zero challenge, as
+ *                        zk_composed_sumcheck_verify. It does NOT check the
+ *                        public tables' entries of table_evals: it returns
+ *                        out_challenges[nrounds] so that the caller can
+ *                        (zk_mle_evaluate, zk_mle_eq_eval), and must.
+ *                        SOUNDNESS: the note on g2_taus at
+ *                        zk_gkr_circuit_verify_kzg applies unchanged: they must
+ *                        come from a setup the verifier trusts, not from the
+ *                        prover.
+ * ZK_EINVAL besides the composed sum-check's: committed_mask = 0, a mask bit
+ * at or above ntables, nvars (nrounds) different from the setup's variable
+ * count (so nvars = 0: KZG needs one variable), a point not on the curve. The
+ * composed caps are unchanged. Nothing is written on failure, the transcript
+ * included.
+ * ------------------------------------------------------------------------- */
+int zk_dev_mle_lincomb(zk_ctx* ctx, zk_field field, zk_repr repr, const void* const* d_tables, uint32_t ntables,
+                       const zk_fe* coeffs /* ntables */, const zk_fe* constant /* may be NULL = 0 */, uint64_t count,
+                       void* d_out);
+int zk_dev_mle_eq_table(zk_ctx* ctx, zk_field field, zk_repr repr, const zk_fe* point, uint32_t n,
+                        void* d_out /* 2^n */);
+int zk_mle_eq_table(zk_ctx* ctx, zk_field field, zk_repr repr, const zk_fe* point, uint32_t n, zk_fe* out /* 2^n */);
+int zk_mle_eq_eval(zk_field field, zk_repr repr, const zk_fe* a, const zk_fe* b, uint32_t n, zk_fe* out);
+int zk_dev_kzg_commit_batch(zk_ctx* ctx, const zk_kzg* kzg, const void* const* d_tables, uint32_t ntables,
+                            zk_g1* out /* ntables */);
+int zk_kzg_commit_batch(zk_ctx* ctx, const zk_kzg* kzg, zk_repr repr, const zk_fe* const* tables, uint32_t ntables,
+                        zk_g1* out /* ntables */);
+int zk_dev_kzg_batch_open(zk_ctx* ctx, const zk_kzg* kzg, zk_repr repr, const void* const* d_tables, uint32_t ntables,
+                          const zk_fe* rho, const zk_fe* opened_values /* ntables */, const zk_fe* point /* nvars */,
+                          zk_g1* out /* nvars */);
+int zk_kzg_batch_open(zk_ctx* ctx, const zk_kzg* kzg, zk_repr repr, const zk_fe* const* tables, uint32_t ntables,
+                      const zk_fe* rho, const zk_fe* opened_values /* ntables */, const zk_fe* point /* nvars */,
+                      zk_g1* out /* nvars */);
+int zk_kzg_batch_verify(zk_repr repr, const zk_g1* commitments, uint32_t ntables, const zk_fe* rho,
+                        const zk_fe* opened_values, const zk_g1* proof, uint32_t nproof, const zk_fe* point,
+                        uint32_t npoint, const zk_g2* g2_taus, int* out_verified);
+int zk_committed_sumcheck_prove(zk_ctx* ctx, const zk_kzg* kzg, zk_repr repr, const zk_fe* const* tables,
+                                uint32_t ntables, uint32_t nvars, const uint8_t* factors, uint32_t nterms,
+                                uint32_t degree, uint32_t committed_mask,
+                                const zk_g1* commitments_in /* NULL: compute them */, const zk_fe* claimed_sum,
+                                zk_transcript* transcript, zk_fe* out_coeffs, uint8_t* out_ncoeffs,
+                                zk_fe* out_challenges, zk_fe* out_table_evals, zk_fe* out_claimed_sum,
+                                zk_g1* out_commitments /* popcount(mask), table-index order */,
+                                zk_g1* out_opening /* nvars */);
+int zk_dev_committed_sumcheck_prove(zk_ctx* ctx, const zk_kzg* kzg, zk_repr repr, const void* const* d_tables,
+                                    uint32_t ntables, uint32_t nvars, const uint8_t* factors, uint32_t nterms,
+                                    uint32_t degree, uint32_t committed_mask, const zk_g1* commitments_in,
+                                    const zk_fe* claimed_sum, zk_transcript* transcript, zk_fe* out_coeffs,
+                                    uint8_t* out_ncoeffs, zk_fe* out_challenges, zk_fe* out_table_evals,
+                                    zk_fe* out_claimed_sum, zk_g1* out_commitments, zk_g1* out_opening);
+int zk_committed_sumcheck_verify(zk_repr repr, uint32_t degree, const zk_fe* coeffs, const uint8_t* ncoeffs,
+                                 uint32_t nrounds, const zk_fe* claimed_sum, const uint8_t* factors, uint32_t nterms,
+                                 uint32_t ntables, const zk_fe* table_evals, uint32_t committed_mask,
+                                 const zk_g1* commitments, const zk_g1* opening, const zk_g2* g2_taus,
+                                 zk_transcript* transcript, int* out_verified, zk_fe* out_challenges);
+
+/* ---------------------------------------------------------------------------
  * Proof blob: a canonical byte form of a proof, so a proof
  * produced on the CPU, on one GPU or on G GPUs can be compared as one digest
  * and shipped/verified elsewhere. The reference keeps proofs as in-memory

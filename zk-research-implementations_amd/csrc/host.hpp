@@ -290,6 +290,12 @@ static_assert(6656 + sizeof(zk::RPost) <= 8192 && 6144 + sizeof(zk::RPost) <= kH
 
 inline void bind(zk_ctx* c) { HIPCK(hipSetDevice(c->device)); }
 void wired_release_all(zk_ctx* c);  // wired.hip: frees c->wired (zk_ctx_destroy)
+// wired.hip (k_eq_table): eq(pt[0..n), .), MSB first as host_eq_table, into dst
+// (2^n entries, n >= 1); tmp holds the tables between passes (2^(n-2) + 8 entries)
+template <class F>
+void eq_table_device(zk_ctx* c, const Fe* pt, uint32_t n, Fe* dst, Fe* tmp);
+uint32_t kzg_nvars(const zk_kzg* k);  // kzg.hip: a setup's variable count
+void check_g1_points(const zk_g1* pts, uint32_t n);  // kzg.hip: ZK_EINVAL unless canonical and on the curve ((0, 0) = infinity)
 
 // At most one resident wave of 256-thread blocks (blocks/CU from the
 // kernel's register budget), grid-striding over the rest: no tail of

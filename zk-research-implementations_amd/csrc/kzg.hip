@@ -5,6 +5,7 @@
 #include <thread>
 
 #include "host.hpp"
+#include "committed.hpp"
 #include "msm.hpp"
 #include "pairing.hpp"
 
@@ -556,8 +557,12 @@ G1J kzg_commit_canonical(zk_ctx* c, const zk_kzg* k, uint32_t v, const Fe* scala
 // element as the reference's commitment of the blown-up quotient against the
 // full basis, since sum_k L_(k, j) over the blown-up top variables is L_j of
 // the suffix basis (eq sums to 1) — then fold f by point[i].
-void kzg_get_proof(zk_ctx* c, const zk_kzg* k, const Fe* f_mont, const Fe& v_mont, const std::vector<Fe>& point,
-                   std::vector<G1J>& out) {
+// The first step, cur = f - v, is the caller's: `fill(cur, N)` writes the N
+// Montgomery values of f - v into the workspace (one k_sub_const for one table,
+// one k_lincomb for a batch, which so needs neither a buffer for the combined
+// table nor a pass of its own).
+template <class Fill>
+void kzg_get_proof_from(zk_ctx* c, const zk_kzg* k, const std::vector<Fe>& point, std::vector<G1J>& out, Fill&& fill) {
   using namespace zk;
   const uint32_t nv = k->nv;
   const uint64_t N = (uint64_t)1 << nv;
@@ -566,7 +571,7 @@ void kzg_get_proof(zk_ctx* c, const zk_kzg* k, const Fe* f_mont, const Fe& v_mon
   Fe* cur = reinterpret_cast<Fe*>(a.p);
   Fe* nxt = cur + N;
   Fe* q = nxt + N / 2;
-  launch(c, ZK_K_FOLD, 64.0 * N, 0, k_sub_const<Fr381>, grid_for(c, N, k_sub_const<Fr381>), f_mont, N, v_mont, cur);
+  fill(cur, N);
   out.assign(nv, g1_inf());
   // the quotients of the last kProofBatchLevels levels (<= 2^19 points each):
   // written at the offsets of their suffix bases and committed together in one
@@ -595,7 +600,89 @@ void kzg_get_proof(zk_ctx* c, const zk_kzg* k, const Fe* f_mont, const Fe& v_mon
     for (uint32_t v = 0; v < nbatch; ++v) out[nv - 1 - v] = lv[v];  // level v = quotient i = nv - 1 - v
   }
 }
+void kzg_get_proof(zk_ctx* c, const zk_kzg* k, const Fe* f_mont, const Fe& v_mont, const std::vector<Fe>& point,
+                   std::vector<G1J>& out) {
+  using namespace zk;
+  kzg_get_proof_from(c, k, point, out, [&](Fe* cur, uint64_t N) {
+    launch(c, ZK_K_FOLD, 64.0 * N, 0, k_sub_const<Fr381>, grid_for(c, N, k_sub_const<Fr381>), f_mont, N, v_mont, cur);
+  });
+}
+
+// What a batch of k tables opened at one point shares (committed_plan.hpp):
+// the weights rho^j and the opened value v = sum_j rho^j values[j], Montgomery.
+struct BatchWeights {
+  Fe pow[zkc::kLincombMaxTables];
+  Fe v;
+};
+BatchWeights batch_weights(zk_repr repr, uint32_t ntables, const zk_fe* rho, const zk_fe* values) {
+  require(ntables >= 1, "ntables must be at least 1");
+  if (ntables > zkc::kLincombMaxTables) fail(ZK_EUNSUPPORTED, "more than 16 tables in a batch");
+  require(repr == ZK_REPR_CANONICAL || repr == ZK_REPR_MONTGOMERY, "unknown repr");
+  BatchWeights w;
+  Fe val[zkc::kLincombMaxTables];
+  for (uint32_t j = 0; j < ntables; ++j) val[j] = in_mont<Fr381>(repr, values[j]);
+  zkc::rho_powers<Fr381>(in_mont<Fr381>(repr, *rho), ntables, w.pow);
+  w.v = zkc::rho_combine<Fr381>(w.pow, val, ntables);
+  return w;
+}
+
+// get_proof(v, point, g) for g = sum_j rho^j table_j, v = sum_j rho^j values[j]
+// (tables Montgomery on the device): g - v goes straight into get_proof's
+// workspace by one k_lincomb with the constant -v.
+void kzg_batch_open(zk_ctx* c, const zk_kzg* k, zk_repr repr, const Fe* const* dT, uint32_t ntables, const zk_fe* rho,
+                    const zk_fe* values, const zk_fe* point, zk_g1* out) {
+  const BatchWeights w = batch_weights(repr, ntables, rho, values);
+  std::vector<Fe> pt(k->nv);
+  for (uint32_t i = 0; i < k->nv; ++i) pt[i] = in_mont<Fr381>(repr, point[i]);
+  const Fe negv = zk::hfe_sub<Fr381>(zk::fe_zero<Fr381>(), w.v);
+  std::vector<G1J> q;
+  kzg_get_proof_from(c, k, pt, q, [&](Fe* cur, uint64_t N) { launch_lincomb<Fr381>(c, dT, ntables, w.pow, negv, N, cur); });
+  const std::vector<G1A> qa = host_normalize(q);
+  for (uint32_t i = 0; i < k->nv; ++i) out[i] = g1a_out(qa[i]);
+}
+
+// KZG::verify (kzg.rs:97-129): e(C - v G1, G2) == sum_i e(q_i, g2_taus[i] - a_i G2)
+// (GT written additively in ark), checked as one product of Miller loops
+// e(C - v G1, G2) * prod_i e(-q_i, g2_taus[i] - a_i G2) with one final
+// exponentiation — the same boolean. v: canonical limbs.
+bool kzg_verify_core(zk_repr repr, const G1J& commitment, const uint32_t v[8], const zk_g1* proof, const zk_fe* point,
+                     uint32_t npoint, const zk_g2* g2_taus) {
+  using namespace zk;
+  const G1J g1 = g1_from_affine(g1_generator());
+  const G2J g2 = g2_from_affine(g2_generator());
+  const G1J lhs = g1_add(commitment, g1_neg(g1_mul(g1, v)));
+  // inputs parsed and checked on this thread (they may throw); the G2 factors
+  // and the Miller loops — independent per point — on host threads, then
+  // one product and one final exponentiation (multi_pairing's value)
+  std::vector<G1A> P(npoint + 1);
+  std::vector<G2A> Q(npoint + 1), tau(npoint);
+  std::vector<std::array<uint32_t, 8>> a(npoint);
+  P[0] = g1_affine(lhs);
+  Q[0] = g2_generator();
+  for (uint32_t i = 0; i < npoint; ++i) {
+    fr_canon(repr, point[i], a[i].data());
+    tau[i] = parse_g2(g2_taus[i]);
+    G1A qi = parse_g1(proof[i]);
+    if (!g1a_is_inf(qi)) qi.y = fq_neg(qi.y);
+    P[i + 1] = qi;
+  }
+  host_parallel(npoint, [&](uint32_t i) {
+    Q[i + 1] = g2_to_affine(g2_add(g2_from_affine(tau[i]), g2_neg(g2_mul(g2, a[i].data()))));
+  });
+  std::vector<Fq12> ml(npoint + 1, fq12_one());
+  host_parallel(npoint + 1, [&](uint32_t i) {
+    if (!g1a_is_inf(P[i]) && !Q[i].inf) ml[i] = miller_loop(P[i], Q[i]);
+  });
+  Fq12 f = fq12_one();
+  for (const Fq12& m : ml) f = fq12_mul(f, m);
+  return fq12_is_one(final_exponentiation(f));
+}
 }  // namespace
+
+uint32_t zkh::kzg_nvars(const zk_kzg* k) { return k->nv; }
+void zkh::check_g1_points(const zk_g1* pts, uint32_t n) {
+  for (uint32_t i = 0; i < n; ++i) (void)parse_g1(pts[i]);
+}
 
 extern "C" {
 
@@ -737,6 +824,78 @@ int zk_dev_kzg_get_proof(zk_ctx* c, const zk_kzg* k, zk_repr repr, const void* d
   });
 }
 
+// ---- batches: k tables committed, and opened at one point by one proof ----
+int zk_dev_kzg_commit_batch(zk_ctx* c, const zk_kzg* k, const void* const* d_tables, uint32_t ntables, zk_g1* out) {
+  return guarded([&] {
+    require(c && k && d_tables && out, "null argument");
+    require(ntables >= 1, "ntables must be at least 1");
+    for (uint32_t i = 0; i < ntables; ++i) require(d_tables[i] != nullptr, "null table");
+    bind(c);
+    const uint64_t N = (uint64_t)1 << k->nv;
+    c->input.ensure(N * 32);  // the one conversion buffer; one MSM per table
+    std::vector<zk_g1> cm(ntables);
+    for (uint32_t i = 0; i < ntables; ++i) {
+      launch(c, ZK_K_CONVERT, 64.0 * N, (double)N, zk::k_convert<Fr381, false>,
+             grid_for(c, N, zk::k_convert<Fr381, false>), reinterpret_cast<const Fe*>(d_tables[i]), c->input.fe(), N);
+      cm[i] = g1_out(kzg_commit_canonical(c, k, k->nv, c->input.fe()));
+    }
+    for (uint32_t i = 0; i < ntables; ++i) out[i] = cm[i];
+  });
+}
+
+int zk_kzg_commit_batch(zk_ctx* c, const zk_kzg* k, zk_repr repr, const zk_fe* const* tables, uint32_t ntables,
+                        zk_g1* out) {
+  return guarded([&] {
+    require(c && k && tables && out, "null argument");
+    require(ntables >= 1, "ntables must be at least 1");
+    require(repr == ZK_REPR_CANONICAL || repr == ZK_REPR_MONTGOMERY, "unknown repr");
+    for (uint32_t i = 0; i < ntables; ++i) require(tables[i] != nullptr, "null table");
+    bind(c);
+    const uint64_t N = (uint64_t)1 << k->nv;
+    c->input.ensure(N * 32);
+    std::vector<zk_g1> cm(ntables);
+    for (uint32_t i = 0; i < ntables; ++i) {
+      upload_fr_canonical(c, repr, tables[i], N, c->input.fe());
+      cm[i] = g1_out(kzg_commit_canonical(c, k, k->nv, c->input.fe()));
+    }
+    for (uint32_t i = 0; i < ntables; ++i) out[i] = cm[i];
+  });
+}
+
+int zk_dev_kzg_batch_open(zk_ctx* c, const zk_kzg* k, zk_repr repr, const void* const* d_tables, uint32_t ntables,
+                          const zk_fe* rho, const zk_fe* opened_values, const zk_fe* point, zk_g1* out) {
+  return guarded([&] {
+    require(c && k && d_tables && rho && opened_values && point && out, "null argument");
+    for (uint32_t i = 0; i < std::min(ntables, zkc::kLincombMaxTables); ++i) require(d_tables[i] != nullptr, "null table");
+    bind(c);
+    std::vector<zk_g1> q(k->nv);
+    kzg_batch_open(c, k, repr, reinterpret_cast<const Fe* const*>(d_tables), ntables, rho, opened_values, point, q.data());
+    for (uint32_t i = 0; i < k->nv; ++i) out[i] = q[i];
+  });
+}
+
+int zk_kzg_batch_open(zk_ctx* c, const zk_kzg* k, zk_repr repr, const zk_fe* const* tables, uint32_t ntables,
+                      const zk_fe* rho, const zk_fe* opened_values, const zk_fe* point, zk_g1* out) {
+  return guarded([&] {
+    require(c && k && tables && rho && opened_values && point && out, "null argument");
+    require(ntables >= 1, "ntables must be at least 1");
+    if (ntables > zkc::kLincombMaxTables) fail(ZK_EUNSUPPORTED, "more than 16 tables in a batch");
+    require(repr == ZK_REPR_CANONICAL || repr == ZK_REPR_MONTGOMERY, "unknown repr");
+    for (uint32_t i = 0; i < ntables; ++i) require(tables[i] != nullptr, "null table");
+    bind(c);
+    const uint64_t N = (uint64_t)1 << k->nv;
+    c->input.ensure((uint64_t)ntables * N * 32);
+    const Fe* dT[zkc::kLincombMaxTables];
+    for (uint32_t i = 0; i < ntables; ++i) {
+      upload<Fr381>(c, repr, tables[i], N, c->input.fe(i * N));
+      dT[i] = c->input.fe(i * N);
+    }
+    std::vector<zk_g1> q(k->nv);
+    kzg_batch_open(c, k, repr, dT, ntables, rho, opened_values, point, q.data());
+    for (uint32_t i = 0; i < k->nv; ++i) out[i] = q[i];
+  });
+}
+
 int zk_kzg_release_fixed_base_cache(int device) {
   return guarded([&] {
     FixedBaseCache& fc = fixed_base_cache();
@@ -821,10 +980,7 @@ int zk_bls12_381_pairing_check(const zk_g1* p, const zk_g2* q, size_t n, int* ou
   });
 }
 
-// KZG::verify (kzg.rs:97-129): e(C - v G1, G2) == sum_i e(q_i, g2_taus[i] - a_i G2)
-// (GT written additively in ark), checked as one product of Miller loops
-// e(C - v G1, G2) * prod_i e(-q_i, g2_taus[i] - a_i G2) with one final
-// exponentiation — the same boolean.
+// KZG::verify (kzg.rs:97-129): kzg_verify_core above.
 int zk_kzg_verify(zk_repr repr, const zk_g1* commitment, const zk_fe* opened_value, const zk_g1* proof,
                   uint32_t nproof, const zk_fe* point, uint32_t npoint, const zk_g2* g2_taus, int* out_verified) {
   return guarded([&] {
@@ -832,37 +988,35 @@ int zk_kzg_verify(zk_repr repr, const zk_g1* commitment, const zk_fe* opened_val
             "null argument");
     // :104-106
     require(nproof == npoint, "num of quotients in proof not equal to num of opening values");
-    using namespace zk;
-    const G1J g1 = g1_from_affine(g1_generator());
-    const G2J g2 = g2_from_affine(g2_generator());
     uint32_t v[8];
     fr_canon(repr, *opened_value, v);
-    const G1J lhs = g1_add(g1_from_affine(parse_g1(*commitment)), g1_neg(g1_mul(g1, v)));
-    // inputs parsed and checked on this thread (they may throw); the G2 factors
-    // and the Miller loops — independent per point — on host threads, then
-    // one product and one final exponentiation (multi_pairing's value)
-    std::vector<G1A> P(npoint + 1);
-    std::vector<G2A> Q(npoint + 1), tau(npoint);
-    std::vector<std::array<uint32_t, 8>> a(npoint);
-    P[0] = g1_affine(lhs);
-    Q[0] = g2_generator();
-    for (uint32_t i = 0; i < npoint; ++i) {
-      fr_canon(repr, point[i], a[i].data());
-      tau[i] = parse_g2(g2_taus[i]);
-      G1A qi = parse_g1(proof[i]);
-      if (!g1a_is_inf(qi)) qi.y = fq_neg(qi.y);
-      P[i + 1] = qi;
-    }
-    host_parallel(npoint, [&](uint32_t i) {
-      Q[i + 1] = g2_to_affine(g2_add(g2_from_affine(tau[i]), g2_neg(g2_mul(g2, a[i].data()))));
+    const G1J c0 = zk::g1_from_affine(parse_g1(*commitment));
+    *out_verified = kzg_verify_core(repr, c0, v, proof, point, npoint, g2_taus) ? 1 : 0;
+  });
+}
+
+// One KZG::verify for k commitments opened at one point: C = sum_j rho^j C_j
+// against v = sum_j rho^j opened_values[j] (batch_weights), host group
+// operations (k scalar multiplications).
+int zk_kzg_batch_verify(zk_repr repr, const zk_g1* commitments, uint32_t ntables, const zk_fe* rho,
+                        const zk_fe* opened_values, const zk_g1* proof, uint32_t nproof, const zk_fe* point,
+                        uint32_t npoint, const zk_g2* g2_taus, int* out_verified) {
+  return guarded([&] {
+    require(commitments && rho && opened_values && out_verified && ((proof && point && g2_taus) || npoint == 0),
+            "null argument");
+    require(nproof == npoint, "num of quotients in proof not equal to num of opening values");
+    const BatchWeights w = batch_weights(repr, ntables, rho, opened_values);
+    std::vector<G1J> cj(ntables);
+    for (uint32_t j = 0; j < ntables; ++j) cj[j] = zk::g1_from_affine(parse_g1(commitments[j]));  // on the curve, (0, 0) = infinity
+    std::vector<G1J> term(ntables);
+    host_parallel(ntables, [&](uint32_t j) {
+      const Fe e = zk::fe_from_mont<Fr381>(w.pow[j]);
+      term[j] = zk::g1_mul(cj[j], e.v);
     });
-    std::vector<Fq12> ml(npoint + 1, fq12_one());
-    host_parallel(npoint + 1, [&](uint32_t i) {
-      if (!g1a_is_inf(P[i]) && !Q[i].inf) ml[i] = miller_loop(P[i], Q[i]);
-    });
-    Fq12 f = fq12_one();
-    for (const Fq12& m : ml) f = fq12_mul(f, m);
-    *out_verified = fq12_is_one(final_exponentiation(f)) ? 1 : 0;
+    G1J sum = zk::g1_inf();
+    for (const G1J& t : term) sum = zk::g1_add(sum, t);
+    const Fe vc = zk::fe_from_mont<Fr381>(w.v);
+    *out_verified = kzg_verify_core(repr, sum, vc.v, proof, point, npoint, g2_taus) ? 1 : 0;
   });
 }
 

@@ -86,10 +86,13 @@ struct WiredOut {
 
 uint32_t blocks_for(uint64_t n) { return (uint32_t)((n + zk::kBlock - 1) / zk::kBlock); }
 
+}  // namespace
+
 // eq(pt[0..n), .) into dst (2^n entries), by doubling in passes of <= 3 coordinates (k_eq_table);
-// the tables between passes live in tmp (< 2^(n-2) + 8 entries in all)
+// the tables between passes live in tmp (< 2^(n-2) + 8 entries in all). n >= 1.
+// Declared in host.hpp: zk_dev_mle_eq_table (committed.hip) builds its table here too.
 template <class F>
-void eq_table_device(zk_ctx* c, const Fe* pt, uint32_t n, Fe* dst, Fe* tmp) {
+void zkh::eq_table_device(zk_ctx* c, const Fe* pt, uint32_t n, Fe* dst, Fe* tmp) {
   const Fe* src = nullptr;
   uint32_t have = 0;
   size_t off = 0;
@@ -109,6 +112,11 @@ void eq_table_device(zk_ctx* c, const Fe* pt, uint32_t n, Fe* dst, Fe* tmp) {
     have += S;
   }
 }
+template void zkh::eq_table_device<zk::Bn254Fr>(zk_ctx*, const Fe*, uint32_t, Fe*, Fe*);
+template void zkh::eq_table_device<zk::Bn254Fq>(zk_ctx*, const Fe*, uint32_t, Fe*, Fe*);
+template void zkh::eq_table_device<zk::Bls12_381Fr>(zk_ctx*, const Fe*, uint32_t, Fe*, Fe*);
+
+namespace {
 
 // sum_j w[j] e[j] over n entries on the device (k_wired_dot), the blocks' parts added here
 template <class F>

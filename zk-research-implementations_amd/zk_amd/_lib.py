@@ -90,6 +90,18 @@ SIGNATURES = {
     "zk_dev_composed_sumcheck_prove": (I, [P, I, I, P, U32, U32, P, U32, U32, P, P, P, P, P, P, P]),
     "zk_composed_sumcheck_verify": (I, [I, I, U32, P, P, U32, P, P, C.POINTER(C.c_int), P, P]),
     "zk_composed_combine": (I, [I, I, P, U32, P, U32, U32, P]),
+    "zk_dev_mle_lincomb": (I, [P, I, I, P, U32, P, P, U64, P]),
+    "zk_dev_mle_eq_table": (I, [P, I, I, P, U32, P]),
+    "zk_mle_eq_table": (I, [P, I, I, P, U32, P]),
+    "zk_mle_eq_eval": (I, [I, I, P, P, U32, P]),
+    "zk_dev_kzg_commit_batch": (I, [P, P, P, U32, P]),
+    "zk_kzg_commit_batch": (I, [P, P, I, P, U32, P]),
+    "zk_dev_kzg_batch_open": (I, [P, P, I, P, U32, P, P, P, P]),
+    "zk_kzg_batch_open": (I, [P, P, I, P, U32, P, P, P, P]),
+    "zk_kzg_batch_verify": (I, [I, P, U32, P, P, P, U32, P, U32, P, C.POINTER(C.c_int)]),
+    "zk_committed_sumcheck_prove": (I, [P, P, I, P, U32, U32, P, U32, U32, U32, P, P, P, P, P, P, P, P, P, P]),
+    "zk_dev_committed_sumcheck_prove": (I, [P, P, I, P, U32, U32, P, U32, U32, U32, P, P, P, P, P, P, P, P, P, P]),
+    "zk_committed_sumcheck_verify": (I, [I, U32, P, P, U32, P, P, U32, U32, P, U32, P, P, P, P, C.POINTER(C.c_int), P]),
     "zk_kzg_setup": (I, [P, I, P, U32, C.POINTER(C.c_void_p)]),
     "zk_kzg_free": (None, [P]),
     "zk_kzg_lagrange_basis": (I, [P, P, U32, P]),

@@ -207,6 +207,28 @@ class MultilinearPoly:
                                   a.shape[0], ptr(b), b.shape[0], ptr(out)))
         return MultilinearPoly(out, field, ctx)
 
+    @staticmethod
+    def eq(point, field: int = Field.BN254_FR, ctx: Context | None = None) -> "MultilinearPoly":
+        """The table eq(point, .) over the 2^len(point) hypercube points, MSB
+        first (zk_mle_eq_table): the public table of a zero-check."""
+        pt = [int(v) for v in point]
+        out = np.zeros((1 << len(pt), 4), np.uint64)
+        _call(lib().zk_mle_eq_table((ctx or default_context()).h, int(field), REPR_CANONICAL,
+                                    ptr(as_limbs(pt)) if pt else None, len(pt), ptr(out)))
+        return MultilinearPoly(out, field, ctx)
+
+    @staticmethod
+    def eq_eval(a, b, field: int = Field.BN254_FR) -> int:
+        """prod_i (a_i b_i + (1 - a_i)(1 - b_i)): eq(a, .) at the point b
+        (zk_mle_eq_eval, host)."""
+        if len(a) != len(b):
+            raise ValueError("eq_eval takes two points of one length")
+        out = np.zeros((1, 4), np.uint64)
+        n = len(a)
+        _call(lib().zk_mle_eq_eval(int(field), REPR_CANONICAL, ptr(as_limbs([int(v) for v in a])) if n else None,
+                                   ptr(as_limbs([int(v) for v in b])) if n else None, n, ptr(out)))
+        return to_ints(out)[0]
+
     def __eq__(self, other) -> bool:
         return (
             isinstance(other, MultilinearPoly)

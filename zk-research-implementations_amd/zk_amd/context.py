@@ -171,3 +171,28 @@ class DeviceTable:
 
     def to_ints(self) -> list[int]:
         return to_ints(self.download())
+
+    @staticmethod
+    def lincomb(tables: list["DeviceTable"], coeffs, constant: int | None = None) -> "DeviceTable":
+        """A new table sum_i coeffs[i] * tables[i] + constant (zk_dev_mle_lincomb):
+        1 to 16 tables of one field and length; a table may repeat."""
+        if not tables or len(coeffs) != len(tables):
+            raise ValueError("one coefficient per table, at least one table")
+        t0 = tables[0]
+        if any(t.count != t0.count or int(t.field) != int(t0.field) or t.ctx is not t0.ctx for t in tables):
+            raise ValueError("the tables must share a context, a field and a length")
+        out = DeviceTable(t0.ctx, t0.field, t0.count)
+        arr = (C.c_void_p * len(tables))(*[t.ptr.value for t in tables])
+        k = ptr(as_limbs([int(constant)])) if constant is not None else None
+        check(lib().zk_dev_mle_lincomb(t0.ctx.h, int(t0.field), REPR_CANONICAL, arr, len(tables),
+                                       ptr(as_limbs([int(x) for x in coeffs])), k, t0.count, out.ptr))
+        return out
+
+    @staticmethod
+    def eq(ctx: Context, field: int, point) -> "DeviceTable":
+        """eq(point, .) over the 2^len(point) hypercube points, MSB first (zk_dev_mle_eq_table)."""
+        pt = [int(v) for v in point]
+        out = DeviceTable(ctx, field, 1 << len(pt))
+        check(lib().zk_dev_mle_eq_table(ctx.h, int(field), REPR_CANONICAL,
+                                        ptr(as_limbs(pt)) if pt else None, len(pt), out.ptr))
+        return out

@@ -136,6 +136,62 @@ class KZG:  # kzg.rs:10-49
                                          ptr(as_limbs([int(v) for v in opening_values])), ptr(out)))
         return _points(out)
 
+    # ---- batches: k tables opened at one point by one proof ----
+    def _device_tables(self, tables) -> "C.Array":
+        for t in tables:
+            if t.count != 1 << self.nvars or int(t.field) != int(FIELD):
+                raise ValueError("every device table must hold 2^nvars BLS12-381 Fr values")
+        return (C.c_void_p * max(len(tables), 1))(*[t.ptr.value for t in tables])
+
+    def commit_batch(self, tables) -> list:
+        """KZG::commit of every table: lists of integers, or DeviceTables
+        (zk_kzg_commit_batch / zk_dev_kzg_commit_batch)."""
+        tables = list(tables)
+        out = np.zeros((max(len(tables), 1), 12), np.uint64)
+        if tables and hasattr(tables[0], "ptr"):
+            _call(lib().zk_dev_kzg_commit_batch(self.ctx.h, self.h, self._device_tables(tables), len(tables), ptr(out)))
+        else:
+            limbs = [as_limbs([int(e) for e in t]) for t in tables]
+            arr = (C.c_void_p * max(len(limbs), 1))(*[a.ctypes.data for a in limbs])
+            _call(lib().zk_kzg_commit_batch(self.ctx.h, self.h, REPR_CANONICAL, arr, len(limbs), ptr(out)))
+        return _points(out)[: len(tables)]
+
+    def batch_open(self, rho: int, opened_values: list[int], opening_values: list[int], tables) -> list:
+        """One get_proof for sum_j rho^j tables[j] at the point opening_values,
+        opened_values[j] being table j there (zk_kzg_batch_open)."""
+        limbs = [as_limbs([int(e) for e in t]) for t in tables]
+        arr = (C.c_void_p * max(len(limbs), 1))(*[a.ctypes.data for a in limbs])
+        out = np.zeros((self.nvars, 12), np.uint64)
+        _call(lib().zk_kzg_batch_open(self.ctx.h, self.h, REPR_CANONICAL, arr, len(limbs), ptr(as_limbs([int(rho)])),
+                                      ptr(_scalars(opened_values)), ptr(_scalars(opening_values)), ptr(out)))
+        return _points(out)
+
+    def batch_open_device(self, rho: int, opened_values: list[int], opening_values: list[int], tables) -> list:
+        """batch_open over DeviceTables: no host upload (zk_dev_kzg_batch_open)."""
+        tables = list(tables)
+        out = np.zeros((self.nvars, 12), np.uint64)
+        _call(lib().zk_dev_kzg_batch_open(self.ctx.h, self.h, REPR_CANONICAL, self._device_tables(tables), len(tables),
+                                          ptr(as_limbs([int(rho)])), ptr(_scalars(opened_values)),
+                                          ptr(_scalars(opening_values)), ptr(out)))
+        return _points(out)
+
+    @staticmethod
+    def batch_verify(commitments: list, rho: int, opened_values: list[int], proof: list, opening_values: list[int],
+                     g2_taus: list) -> bool:
+        """KZG::verify of sum_j rho^j commitments[j] against sum_j rho^j
+        opened_values[j] (zk_kzg_batch_verify, host)."""
+        ok = C.c_int(0)
+        n = len(opening_values)
+        _call(lib().zk_kzg_batch_verify(REPR_CANONICAL, ptr(_g1_array(list(commitments))), len(commitments),
+                                        ptr(as_limbs([int(rho)])), ptr(_scalars(opened_values)), ptr(_g1_array(proof)),
+                                        len(proof), ptr(_scalars(opening_values)), n,
+                                        ptr(_g2_array(list(g2_taus)[:n])), C.byref(ok)))
+        return bool(ok.value)
+
+
+def _scalars(values) -> np.ndarray:
+    return as_limbs([int(v) for v in values]) if len(values) else np.zeros((1, 4), np.uint64)
+
 
 def release_fixed_base_cache(device: int = -1) -> None:
     """Free the per-device fixed-base table large setups share (654 MB of HBM;
