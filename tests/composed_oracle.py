@@ -94,6 +94,10 @@ SHAPES = {
     "deg3_shared": (4, [[0, 1, 2], [0, 3, 3]]),   # table 0 in both terms, table 3 twice in one
     "deg4": (5, [[0, 1, 2, 3], [4, 4, 0, 1]]),
     "repeat": (2, [[0, 0, 1]]),                   # a factor repeated within a term
+    "unused1": (5, [[0, 2]]),                     # tables 1, 3 and 4 are in no term
+    "unused15": (16, [[7]] * 16),                 # degree 1, 15 unused tables: the unused list is full
+    "caps": (16, [[(t + d) % 16 for d in range(4)] for t in range(16)]),  # 16 tables, 16 terms, degree 4
+    "caps_one_table": (16, [[3, 3, 3, 3]] * 16),  # the caps with one table named 64 times, 15 unused
 }
 
 

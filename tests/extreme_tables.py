@@ -161,3 +161,81 @@ def family(name: str, field: int, n: int) -> list[Table]:
     """The four tables (A, S, M, P) of family `name` over 2^n elements, n >= 3."""
     assert n >= 3
     return FAMILIES[name](field, n)
+
+
+# ---------------------------------------------------------------------------
+# The boundary palette and the table families of the composed sum-check
+# ---------------------------------------------------------------------------
+def palette(field: int) -> list[int]:
+    """The boundary words a table can hold in memory, all below p, sorted: the
+    ends and the middle of [0, p); R mod p (the image of 1) with its
+    neighbours and R^2 mod p; around every 32-bit limb boundary from below
+    (2^(32k), 2^(32k) - 1) and from above (p - 2^(32k), p - 2^(32k) + 1), whose
+    sums and differences carry or borrow through k limbs; the word whose low
+    seven limbs are all ones under the largest top limb that keeps it below p;
+    sat+ and sat-. 42 words in each of the three fields."""
+    p = modulus(field)
+    r = R % p
+    words = {0, 1, 2, p - 1, p - 2, (p - 1) // 2, (p + 1) // 2, r, r - 1, r + 1, r * r % p}
+    for k in range(1, 8):
+        words |= {w for w in (1 << 32 * k, (1 << 32 * k) - 1, p - (1 << 32 * k), p - (1 << 32 * k) + 1) if 0 <= w < p}
+    words.add((((p >> 224) - 1) << 224) | ((1 << 224) - 1))
+    s = specials(field)
+    words |= {s["sat+"], s["sat-"]}
+    assert all(0 <= w < p for w in words)
+    return sorted(words)
+
+
+SPRINKLE_POOL = 211  # synth words a `sprinkled` composed table draws from (a prime, so no stride lines up with it)
+
+
+def _all_bits_parity(nvars: int) -> np.ndarray:
+    x = np.arange(1 << nvars, dtype=np.int64)
+    for s in (32, 16, 8, 4, 2, 1):
+        x ^= x >> s
+    return (x & 1).astype(np.intp)
+
+
+def _composed_table(name: str, field: int, t: int, nvars: int, seed: int) -> Table:
+    p, n = modulus(field), 1 << nvars
+    if name == "const_pm1":
+        return Table(field, [p - 1], np.zeros(n, np.intp))
+    if name == "const_sat":
+        return Table(field, [specials(field)["sat-"]], np.zeros(n, np.intp))
+    if name == "checker_pm1":
+        par = _all_bits_parity(nvars)
+        return Table(field, [0, p - 1], par if t % 2 == 0 else 1 - par)
+    pal = palette(field)
+    i = np.arange(n, dtype=np.int64)
+    if name == "palette_cycle":
+        return Table(field, pal, ((i * (2 * t + 1)) % len(pal)).astype(np.intp))
+    assert name == "sprinkled"
+    import coracle as co
+
+    pool = ints(co.synth(field, seed, t, 0, SPRINKLE_POOL))  # (below p: valid words as they are)
+    index = np.random.default_rng(1000 * seed + t).integers(0, SPRINKLE_POOL, n).astype(np.intp)
+    stride = 37 if t % 2 == 0 else 41
+    at = np.arange(0, n, stride)
+    index[at] = SPRINKLE_POOL + (at // stride) % len(pal)
+    return Table(field, pool + pal, index)
+
+
+COMPOSED_FAMILIES = ("const_pm1", "const_sat", "checker_pm1", "sprinkled", "palette_cycle")
+
+
+def composed_family(name: str, field: int, ntables: int, nvars: int, seed: int = 29) -> list[Table]:
+    """`ntables` tables of 2^nvars words for the composed sum-check, each a
+    palette plus an index array (no per-element Python work at size):
+      const_pm1      every word p - 1
+      const_sat      every word sat-
+      checker_pm1    0 or p - 1 by the parity of ALL index bits, even-numbered
+                     tables the complement of odd-numbered ones: both hi - lo
+                     and lo - hi occur in every pair, and the pattern survives
+                     every fold (a top-bit checker is gone after one round)
+      sprinkled      synth words (SPRINKLE_POOL of them per table, drawn by a
+                     seeded index) with a palette word at every 37th index
+                     (41st in odd-numbered tables)
+      palette_cycle  element i of table t is palette word (i (2t + 1)) mod 42
+    """
+    assert name in COMPOSED_FAMILIES
+    return [_composed_table(name, field, t, nvars, seed) for t in range(ntables)]

@@ -350,3 +350,45 @@ def test_family_patterns(field):
     A, S, _, _ = (t.word_ints() for t in xt.family("sprinkled", field, 9))
     assert [A[i] for i in range(0, 512, 37)] == [sp[k % 7] for k in range(14)]
     assert [S[i] for i in range(0, 512, 41)] == [sp[k % 7] for k in range(13)]
+
+
+# ---------------------------------------------------------------------------
+# the boundary palette and the composed families
+# ---------------------------------------------------------------------------
+@pytest.mark.parametrize("field", FIELDS)
+def test_palette(field):
+    p, s = xt.modulus(field), xt.specials(field)
+    pal = xt.palette(field)
+    assert len(pal) == len(set(pal)) == 42 and pal == sorted(pal) and all(0 <= w < p for w in pal)
+    r = xt.R % p
+    must = [0, 1, 2, p - 1, p - 2, (p - 1) // 2, (p + 1) // 2, r - 1, r, r + 1, r * r % p, s["sat+"], s["sat-"]]
+    for k in range(1, 8):  # (2^224 < p in all three fields: every one of them lies in [0, p))
+        must += [1 << 32 * k, (1 << 32 * k) - 1, p - (1 << 32 * k), p - (1 << 32 * k) + 1]
+    ones = [w for w in pal if w & ((1 << 224) - 1) == (1 << 224) - 1 and w >> 224]  # (2^224 - 1 is one of `must`)
+    assert set(must) < set(pal) and len(set(must)) == 41 and ones == [p - (p & ((1 << 224) - 1)) - 1]
+
+
+@pytest.mark.parametrize("field", FIELDS)
+@pytest.mark.parametrize("name", xt.COMPOSED_FAMILIES)
+def test_composed_family_words(field, name):
+    p, pal, s = xt.modulus(field), xt.palette(field), xt.specials(field)
+    for ntables, nvars in ((1, 1), (5, 7), (16, 3)):
+        tabs = xt.composed_family(name, field, ntables, nvars)
+        assert len(tabs) == ntables
+        for t, tab in enumerate(tabs):
+            words, canon = tab.word_ints(), tab.canon_ints()
+            assert len(words) == len(canon) == 1 << nvars
+            assert all(0 <= w < p and c < p and c * xt.R % p == w for w, c in zip(words, canon))
+            if name.startswith("const"):
+                assert set(words) == {p - 1 if name == "const_pm1" else s["sat-"]}
+            elif name == "checker_pm1":
+                assert words == [(p - 1) if (bin(i).count("1") + t) & 1 else 0 for i in range(1 << nvars)]
+            elif name == "palette_cycle":
+                assert words == [pal[i * (2 * t + 1) % 42] for i in range(1 << nvars)]
+            else:
+                stride = 41 if t & 1 else 37
+                assert [words[i] for i in range(0, 1 << nvars, stride)] == \
+                    [pal[k % 42] for k in range(((1 << nvars) + stride - 1) // stride)]
+    if name == "sprinkled":  # between the palette words: many distinct synth words, and another table, other words
+        a, b = (tab.word_ints() for tab in xt.composed_family(name, field, 2, 9))
+        assert len(set(a)) > 150 and len(set(a) & set(b)) <= 42
