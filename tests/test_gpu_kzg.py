@@ -128,9 +128,19 @@ def test_msm_ragged_multi_block_signed_digits(ctx):
     repeated bases (equal points meet in a bucket: the XYZZ doubling and
     cancellation cases), with scalars that hit the signed-digit edges: every
     window at 2^(c-1) (bucket 0's magnitude), every bit set (a carry through
-    every window), r - 1, 0 and 1. Oracle: sum_i s_i k_i * G for bases k_i G."""
+    every window), r - 1, 0 and 1. Oracle: sum_i s_i k_i * G for bases k_i G.
+
+    msm_window_bits gives this n the width c = 10 (26 windows of 2^9 buckets;
+    restated and pinned in tests/ec_cases.py, tests/test_ec_cases_cpu.py), so
+    the edges are those of width 10: its whole scalar family
+    (ec_cases.scalar_family) is sprinkled in. The scalars built for c = 12, the
+    width an earlier cost model chose, stay: at width 10 they are ordinary
+    scalars. tests/test_gpu_kzg_edges.py sweeps every width."""
+    import ec_cases as ec
+
     rng = random.Random(21)
-    n = 2 * 16384 + 777  # c = 12: 22 windows, 2^11 buckets each
+    n = 2 * 16384 + 777
+    assert ec.msm_window_bits(n) == 10
     ks = [1, 2, 3, 5, 8, 13, 21]
     pts = [ko.mul(k, ko.G1) for k in ks]
     c = 12
@@ -139,6 +149,8 @@ def test_msm_ragged_multi_block_signed_digits(ctx):
     scalars = [rng.randrange(R) for _ in range(n)]
     for i, v in enumerate(special * 50):
         scalars[(i * 977) % n] = v % R
+    for i, v in enumerate(ec.scalar_family(10) * 7):  # (each member seven times, at indices the loop above leaves alone)
+        scalars[(i * 977 + 500) % n] = v
     bases = [pts[i % len(ks)] for i in range(n)]
     want = sum(s * ks[i % len(ks)] for i, s in enumerate(scalars)) % R
     assert msm_g1(bases, scalars, ctx) == ko.mul(want, ko.G1)
