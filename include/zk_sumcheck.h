@@ -561,6 +561,125 @@ int zk_committed_sumcheck_verify(zk_repr repr, uint32_t degree, const zk_fe* coe
                                  zk_transcript* transcript, int* out_verified, zk_fe* out_challenges);
 
 /* ---------------------------------------------------------------------------
+ * R1CS satisfiability by two sum-checks over a committed witness (DESIGN.md
+ * 6k; the Spartan reduction, Setty 2020, without the commitment to the
+ * matrices: the verifier is O(entries)). Any field; the KZG closing is
+ * BLS12-381 Fr, as all KZG here.
+ *
+ * The statement. nrows >= 1 constraints (A z)_i (B z)_i = (C z)_i. z has 2^sy
+ * entries: the first half (MSB = 0) is the witness w of 2^(sy-1) entries, the
+ * second half is (1, io_0 .. io_(npub-1), 0 ..), npub + 1 <= 2^(sy-1). Each
+ * matrix is a list of (row, col, value) in any order; duplicates of a
+ * (row, col) inside one matrix add up; zero values are allowed. sx =
+ * max(1, ceil log2 nrows); rows are zero-padded to 2^sx.
+ * Caps: sx, sy <= 24 and at most 2^26 entries in all (ZK_EUNSUPPORTED above).
+ * ZK_EINVAL: nrows = 0, sy = 0, a row >= nrows, a column >= 2^sy, a value >= p,
+ * npub + 1 > 2^(sy-1), an unknown field or repr, a null pointer.
+ *
+ * The transcript, on the caller's handle:
+ *   1. digest = Keccak-256 of: the ASCII bytes "zk-r1cs-v1"; then as u32
+ *      little-endian field, nrows, sx, sy, npub; then for A, B, C in turn the
+ *      u32 entry count and each entry in the caller's order as u32 row, u32
+ *      col and the value's 32 canonical little-endian bytes. Computed at
+ *      handle creation;
+ *   2. append(digest), append(fq_vec_to_bytes(io)) and, with a KZG setup, the
+ *      96 bytes of the commitment of w (the committed sum-check's encoding,
+ *      infinity 96 zero bytes);
+ *   3. tau_0 .. tau_(sx-1) by sx consecutive get_random_challenge;
+ *   4. sum-check 1, exactly as zk_composed_sumcheck_prove runs it: tables
+ *      [eq(tau,.), Az, Bz, -eq(tau,.), Cz, 1], factors {0,1,2},{3,4,5}, degree
+ *      3, claimed sum 0. Its challenges are rx; va, vb, vc = Az, Bz, Cz at rx;
+ *   5. append(fq_vec_to_bytes([va, vb, vc])), rho = get_random_challenge;
+ *   6. M(y) = sum_x eq(rx, x) (A + rho B + rho^2 C)(x, y) over the 2^sy columns;
+ *   7. sum-check 2: tables [M, z], factors {0,1}, degree 2, claimed sum
+ *      va + rho vb + rho^2 vc. Its challenges are ry;
+ *   8. vw = w~(ry[1..]), append(fq_vec_to_bytes([vw])). With a KZG setup of
+ *      sy - 1 variables (so sy >= 2) the opening is get_proof(w, vw, ry[1..]);
+ *      without one the proof ends in the claim (ry[1..], vw), which the caller
+ *      checks, as zk_composed_sumcheck_verify leaves table_evals to the caller.
+ * A proof: coeffs1[4 sx] / ncoeffs1[sx] and coeffs2[3 sy] / ncoeffs2[sy] (the
+ * round polynomials, degree + 1 slots per round, zero past the trimmed count),
+ * evals[4] = (va, vb, vc, vw) and, committed, the commitment and sy - 1
+ * quotient commitments.
+ *
+ *   zk_r1cs_new     nnz[3]: the entry counts of A, B, C; rows / cols / vals:
+ *                   their entries concatenated, A's then B's then C's. With a
+ *                   context the two groupings of the entries (by row, by
+ *                   column) and their values go to the device; the handle
+ *                   works through that context: use it only while the context
+ *                   lives (zk_r1cs_free itself does not read the context). With
+ *                   ctx == NULL the handle is host-only: it verifies, with an
+ *                   O(entries) host evaluation of the three matrices, and
+ *                   multiplies on the host, but cannot prove (ZK_EDEVICE).
+ *   zk_r1cs_shape   sx, sy, the round counts of the two sum-checks (sx and
+ *                   sy) and the digest; any output may be NULL.
+ *   zk_r1cs_mul / zk_dev_r1cs_mul   z (2^sy) -> Az, Bz, Cz, 2^sx entries each
+ *                   (zero in the padded rows). The device entry takes and
+ *                   fills Montgomery tables on the device, none of them
+ *                   overlapping another.
+ *   zk_dev_r1cs_mul_t   the transposes: x (2^sx, Montgomery, on the device) ->
+ *                   A^T x, B^T x, C^T x, 2^sy entries each (zero in columns
+ *                   without entries): the column pass with the three sums kept
+ *                   apart, which the prover runs on x = eq(rx, .).
+ *   zk_r1cs_matrix_evals  out[3] = the multilinear extensions of A, B, C at
+ *                   (rx[sx], ry[sy]): on the device when the handle has a
+ *                   context (the column pass, then three dot products), on the
+ *                   host otherwise.
+ *   zk_r1cs_prove / zk_dev_r1cs_prove   witness: 2^(sy-1) entries in host /
+ *                   device (Montgomery) memory, only read; io[npub] in host
+ *                   memory (NULL when npub = 0). kzg NULL: uncommitted, and
+ *                   commitment_in, out_commitment, out_opening are ignored.
+ *                   With a setup (BLS12-381 Fr, sy - 1 variables; else
+ *                   ZK_EINVAL) commitment_in (NULL: compute it) is absorbed and
+ *                   returned as given, only checked to be on the curve. Writes
+ *                   the proof, out_rx[sx] and out_ry[sy]. The instance need
+ *                   not be satisfied: the proof of an unsatisfied one is
+ *                   rejected.
+ *   zk_r1cs_verify  *out_verified = 1 requires all of: zk_composed_sumcheck_verify
+ *                   accepts both lists of rounds; final_1 == eq(tau, rx)
+ *                   (va vb - vc); final_2 == (A~ + rho B~ + rho^2 C~)(rx, ry) vz
+ *                   with vz = (1 - ry_0) vw + ry_0 pub~(ry[1..]), the public
+ *                   part summed over its npub + 1 non-zero entries; and, with a
+ *                   commitment, zk_kzg_verify of the opening at ry[1..].
+ *                   commitment, opening and g2_taus are all given or all NULL;
+ *                   uncommitted, the caller checks w~(out_ry[1..]) == evals[3].
+ *                   A rejection is ZK_OK with *out_verified = 0 and nothing
+ *                   else written, the transcript included.
+ *                   SOUNDNESS: the note on g2_taus at zk_gkr_circuit_verify_kzg
+ *                   applies unchanged: they must come from a setup the
+ *                   verifier trusts, not from the prover.
+ * Every call works on a copy of the transcript and hands it back only on
+ * success: nothing is written on failure.
+ * ------------------------------------------------------------------------- */
+typedef struct zk_r1cs zk_r1cs;
+int zk_r1cs_new(zk_ctx* ctx /* NULL: host-only */, zk_field field, zk_repr repr, uint32_t nrows, uint32_t sy,
+                uint32_t npub, const uint32_t nnz[3], const uint32_t* rows, const uint32_t* cols, const zk_fe* vals,
+                zk_r1cs** out);
+void zk_r1cs_free(zk_r1cs* r);
+int zk_r1cs_shape(const zk_r1cs* r, uint32_t* out_sx, uint32_t* out_sy, uint32_t* out_rounds1, uint32_t* out_rounds2,
+                  uint8_t out_digest[32]);
+int zk_r1cs_mul(zk_r1cs* r, zk_repr repr, const zk_fe* z /* 2^sy */, zk_fe* out_az, zk_fe* out_bz,
+                zk_fe* out_cz /* 2^sx each */);
+int zk_dev_r1cs_mul(zk_r1cs* r, const void* d_z, void* d_az, void* d_bz, void* d_cz);
+int zk_dev_r1cs_mul_t(zk_r1cs* r, const void* d_x /* 2^sx */, void* d_atx, void* d_btx, void* d_ctx /* 2^sy each */);
+int zk_r1cs_matrix_evals(zk_r1cs* r, zk_repr repr, const zk_fe* rx /* sx */, const zk_fe* ry /* sy */,
+                         zk_fe out[3]);
+int zk_r1cs_prove(zk_r1cs* r, zk_repr repr, const zk_fe* witness /* 2^(sy-1) */, const zk_fe* io /* npub */,
+                  const zk_kzg* kzg /* may be NULL */, const zk_g1* commitment_in /* NULL: compute it */,
+                  zk_transcript* transcript, zk_fe* out_coeffs1 /* 4 sx */, uint8_t* out_ncoeffs1 /* sx */,
+                  zk_fe* out_coeffs2 /* 3 sy */, uint8_t* out_ncoeffs2 /* sy */, zk_fe out_evals[4],
+                  zk_fe* out_rx /* sx */, zk_fe* out_ry /* sy */, zk_g1* out_commitment,
+                  zk_g1* out_opening /* sy - 1 */);
+int zk_dev_r1cs_prove(zk_r1cs* r, zk_repr repr, const void* d_witness, const zk_fe* io, const zk_kzg* kzg,
+                      const zk_g1* commitment_in, zk_transcript* transcript, zk_fe* out_coeffs1,
+                      uint8_t* out_ncoeffs1, zk_fe* out_coeffs2, uint8_t* out_ncoeffs2, zk_fe out_evals[4],
+                      zk_fe* out_rx, zk_fe* out_ry, zk_g1* out_commitment, zk_g1* out_opening);
+int zk_r1cs_verify(zk_r1cs* r, zk_repr repr, const zk_fe* io, const zk_fe* coeffs1, const uint8_t* ncoeffs1,
+                   const zk_fe* coeffs2, const uint8_t* ncoeffs2, const zk_fe evals[4],
+                   const zk_g1* commitment /* NULL: uncommitted */, const zk_g1* opening, const zk_g2* g2_taus,
+                   zk_transcript* transcript, int* out_verified, zk_fe* out_rx /* sx */, zk_fe* out_ry /* sy */);
+
+/* ---------------------------------------------------------------------------
  * Proof blob: a canonical byte form of a proof, so a proof
  * produced on the CPU, on one GPU or on G GPUs can be compared as one digest
  * and shipped/verified elsewhere. The reference keeps proofs as in-memory

@@ -102,6 +102,16 @@ SIGNATURES = {
     "zk_committed_sumcheck_prove": (I, [P, P, I, P, U32, U32, P, U32, U32, U32, P, P, P, P, P, P, P, P, P, P]),
     "zk_dev_committed_sumcheck_prove": (I, [P, P, I, P, U32, U32, P, U32, U32, U32, P, P, P, P, P, P, P, P, P, P]),
     "zk_committed_sumcheck_verify": (I, [I, U32, P, P, U32, P, P, U32, U32, P, U32, P, P, P, P, C.POINTER(C.c_int), P]),
+    "zk_r1cs_new": (I, [P, I, I, U32, U32, U32, P, P, P, P, C.POINTER(C.c_void_p)]),
+    "zk_r1cs_free": (None, [P]),
+    "zk_r1cs_shape": (I, [P, C.POINTER(U32), C.POINTER(U32), C.POINTER(U32), C.POINTER(U32), P]),
+    "zk_r1cs_mul": (I, [P, I, P, P, P, P]),
+    "zk_dev_r1cs_mul": (I, [P, P, P, P, P]),
+    "zk_dev_r1cs_mul_t": (I, [P, P, P, P, P]),
+    "zk_r1cs_matrix_evals": (I, [P, I, P, P, P]),
+    "zk_r1cs_prove": (I, [P, I, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
+    "zk_dev_r1cs_prove": (I, [P, I, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
+    "zk_r1cs_verify": (I, [P, I, P, P, P, P, P, P, P, P, P, P, C.POINTER(C.c_int), P, P]),
     "zk_kzg_setup": (I, [P, I, P, U32, C.POINTER(C.c_void_p)]),
     "zk_kzg_free": (None, [P]),
     "zk_kzg_lagrange_basis": (I, [P, P, U32, P]),
