@@ -83,11 +83,43 @@ def tree_plan(n):
     return pl
 
 
-def tree_split(log_len):
+def tree_split(log_len, split=TREE_SPLIT):
+    """poly_tree_split with kPolyTreeSplit = `split` (the build's: the default)."""
     length = 1 << log_len
     if 2 * length <= BLOCK:
         return 1
-    return max(1, min(TREE_SPLIT, length // TREE_TILE))
+    return max(1, min(split, length // TREE_TILE))
+
+
+def tree_steps(n, log_len):
+    """The steps of its left operand each multiplying block of a level with
+    2 len > BLOCK takes before they are dealt over blockIdx.y (the trips of
+    k_poly_tree_level's i0 loop), one entry per tile; no such block: []."""
+    length = 1 << log_len
+    if 2 * length <= BLOCK:
+        return []
+    steps = []
+    for g0 in range(0, n, BLOCK):
+        off = (g0 >> (log_len + 1)) << (log_len + 1)
+        rem = n - off
+        if rem <= length:
+            continue
+        a, b = length, min(rem - length, length)
+        k0 = g0 - off
+        i_min = k0 - b + 1 if k0 >= b else 0
+        steps.append(ceil_div(min(k0 + BLOCK, a) - i_min, TREE_TILE))
+    return steps
+
+
+def tree_most_steps(n):
+    """(steps, log_len, parts): the most steps one block of the tree over n
+    points takes, at the highest level where it does, and that level's parts."""
+    best = (0, 0, 1)
+    for (log_len, *_rest) in tree_plan(n):
+        most = max(tree_steps(n, log_len), default=0)
+        if most >= best[0] and most > 0:
+            best = (most, log_len, tree_split(log_len))
+    return best
 
 
 # --- k_poly_eval / k_poly_eval_combine -----------------------------------------------
@@ -187,12 +219,12 @@ def leaves(p, xs, ys, num_cus, grid_x=None):
 
 
 # --- k_poly_tree_level ----------------------------------------------------------------
-def tree_level(p, Min, Nin, n, log_len, grid_x=None):
+def tree_level(p, Min, Nin, n, log_len, grid_x=None, split=TREE_SPLIT):
     T, W = TREE_TILE, TREE_TILE + BLOCK
     Mi, Ni = _Table(n, Min), _Table(n, Nin)
     Mo, No = _Table(n), _Table(n)
     length = 1 << log_len
-    S = tree_split(log_len)  # gridDim.y
+    S = tree_split(log_len, split)  # gridDim.y
     Mp, Np = _Table(S * n), _Table(S * n)
     tiles = ceil_div(n, BLOCK)
     gx = min(grid_x or tiles, tiles)
@@ -317,9 +349,10 @@ def tree_level(p, Min, Nin, n, log_len, grid_x=None):
     return Mo.v, No.v
 
 
-def interpolate(p, points, num_cus=256, grid_x=None):
+def interpolate(p, points, num_cus=256, grid_x=None, split=TREE_SPLIT):
     """The device path end to end: weights, leaves, the levels of tree_plan,
-    trim. Raises ZeroDivisionError where the library returns ZK_EINVAL."""
+    trim. Raises ZeroDivisionError where the library returns ZK_EINVAL. `split`
+    stands in for kPolyTreeSplit (a smaller one wraps the deal at smaller n)."""
     n = len(points)
     if n == 0:
         return []
@@ -327,7 +360,7 @@ def interpolate(p, points, num_cus=256, grid_x=None):
     if dup:
         raise ZeroDivisionError("two points with the same x")
     for (log_len, *_rest) in tree_plan(n):
-        M, N = tree_level(p, M, N, n, log_len, grid_x)
+        M, N = tree_level(p, M, N, n, log_len, grid_x, split)
     while N and N[-1] == 0:
         N.pop()
     return N

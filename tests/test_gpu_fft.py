@@ -3,14 +3,16 @@ restated in tests/fft_oracle.py. The result is an exact field element, so every
 check is equality: the reference's own three tests, every power of two through
 the single-pass path and the smallest two-pass shapes, multi-pass plans forced
 at small sizes by ZK_FFT_STAGES, the grid-stride path, the default plan at its
-three-pass depth against tests/golden/fft.json and against closed forms, the
-device-table API, and the polynomial product against the schoolbook."""
+three-pass depth against tests/golden/fft.json and against closed forms, at
+its four-pass depth (2^25) against the Horner kernel, the device-table API, and
+the polynomial product against the schoolbook."""
 from __future__ import annotations
 
 import ctypes as C
 import functools
 import json
 import os
+import random
 
 import numpy as np
 import pytest
@@ -21,7 +23,7 @@ import pyoracle as po
 from conftest import ROOT
 
 import zk_amd
-from zk_amd import _lib, fft
+from zk_amd import _lib, fft, poly
 from zk_amd.api import UnivariatePoly
 from zk_amd.elems import as_limbs, ptr, to_ints
 
@@ -228,6 +230,51 @@ def test_default_plan_closed_forms(ctx, field):
         for c in reversed(x):
             acc = (acc * pt + c) % p
         assert y[k] == acc, k
+
+
+def _rows(table, ks) -> list:
+    """Rows ks of a device table as canonical ints, one 32-byte download each."""
+    out = np.zeros((1, 4), np.uint64)
+    got = []
+    for k in ks:
+        assert 0 <= k < table.count
+        assert _lib.lib().zk_dev_download(table.ctx.h, table.field, CANON, C.c_void_p(table.ptr.value + 32 * k), 1, ptr(out)) == 0
+        got.append(to_ints(out)[0])
+    return got
+
+
+@pytest.mark.parametrize("field", FR_FIELDS)
+def test_default_plan_four_passes(ctx, field):
+    """2^25, the first size of the default plan with four passes (widths 7, 6,
+    6, 6, the last pass at Ns = 2^19, the twiddle split at h = 13), 1 GiB a
+    table, device API only. No Python oracle can run this size: the reference
+    is the Horner kernel (poly.dev_evaluate at eight of the 2^25-th roots
+    against the same rows of the transform), which tests/poly_oracle.py pins at
+    small sizes and tests/test_gpu_poly_scale.py at chunks of many staging
+    trips; the input is pinned to the host's synth at seeded rows. A random
+    table has no output with an O(1) closed form, so none is checked. The
+    inverse runs in place (both scratch tables) and must give the input back,
+    every word of it, compared in Montgomery form as downloaded."""
+    p = po.MODULI[field]
+    k = 25
+    n = 1 << k
+    passes = -(-k // T)
+    widths = [k // passes + (1 if i < k % passes else 0) for i in range(passes)]
+    assert passes == 4 and widths == [7, 6, 6, 6] and sum(widths[:-1]) == 19 and (k + 1) // 2 == 13  # fft_plan.hpp, fft.hip
+    rng = random.Random(SEED + field)
+    x = _dev(ctx, field, n)
+    at = [0, 1, n // 2, n - 1] + [rng.randrange(n) for _ in range(4)]
+    assert _rows(x, at) == [co.from_limbs(co.synth(field, SEED, 0, i, 1))[0] for i in at]
+    y = fft.dev_fft(x)
+    w = fo.root_of_unity(field, n)
+    ks = [0, 1, 3, 1 << 24, (1 << 24) + 1, n - 5, n - 1, rng.randrange(n)]
+    pts = ctx.upload(field, [pow(w, e, p) for e in ks])
+    assert _rows(y, ks) == poly.dev_evaluate(x, pts).to_ints()
+    before = x.download(MONT)
+    assert fft.dev_fft(y, inverse=True, out=y) is y  # in place
+    assert np.array_equal(y.download(MONT), before)
+    x.free()
+    y.free()
 
 
 # --- the device API --------------------------------------------------------------------------

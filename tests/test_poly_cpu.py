@@ -10,6 +10,7 @@ plans against the oracle."""
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import json
 import os
 import subprocess
@@ -44,6 +45,12 @@ def _points(field: int, n: int, seed: int = 23):
     if n > 1:
         xs[1] = 0
     return list(zip(xs, ys))
+
+
+@functools.lru_cache(maxsize=None)
+def _fast(field: int, n: int, seed: int) -> tuple:
+    """interpolate_fast of _points, computed once for the tests that share a shape (never modified)."""
+    return tuple(O.interpolate_fast(po.MODULI[field], _points(field, n, seed)))
 
 
 # --- the two oracles ------------------------------------------------------------------
@@ -293,7 +300,7 @@ def test_tree_model_grid_stride(n, grid_x):
     p = po.MODULI[field]
     pts = _points(field, n, seed=31)
     assert tm.ceil_div(n, tm.BLOCK) > grid_x
-    assert tm.interpolate(p, pts, num_cus=8, grid_x=grid_x) == O.interpolate_fast(p, pts)
+    assert tm.interpolate(p, pts, num_cus=8, grid_x=grid_x) == list(_fast(field, n, 31))
 
 
 @pytest.mark.parametrize("m,d,grid_x", [(1025, 100, 3), (700, 1553, 2), (600, 513, 1)])
@@ -314,3 +321,65 @@ def test_eval_model_equals_oracle(m, d):
     want = [O.horner(p, cf, x) for x in xs]
     assert tm.evaluate(p, cf, xs, 256) == want == tm.evaluate(p, cf, xs, 8, grid_x=3)
     assert want[0] == O.evaluate(p, cf, xs[0])
+
+
+# --- paths the plans of a 256-CU device reach only at sizes the model cannot afford -----------
+def test_eval_model_second_staging_trip():
+    """One chunk of more than kPolyEvalTile coefficients with the build's own
+    constants: on one CU five point tiles are already 4 CUs' worth, so 1 100
+    coefficients stay one run and the staging loop of k_poly_eval takes three
+    trips (512, 512, 76), the stage refilled after the trailing barrier."""
+    field, m, d = 1, 1025, 1100
+    p = po.MODULI[field]
+    assert tm.eval_plan(m, d, 1) == (1, d) and d > 2 * tm.EVAL_TILE and d % tm.EVAL_TILE
+    cf = co.from_limbs(co.synth(field, 31, 2, 0, d))
+    xs = ([0, 1, p - 1] + co.from_limbs(co.synth(field, 31, 3, 0, m)))[:m]
+    assert tm.evaluate(p, cf, xs, num_cus=1) == [O.horner(p, cf, x) for x in xs]
+
+
+@pytest.mark.parametrize("n", [1025, 1536])
+def test_tree_model_wrapped_deal(plans, n):
+    """The round-robin deal of a large level's steps with more steps than parts:
+    with the split constant lowered to 2 a block of a level with len >= 512
+    takes up to four (n = 1 025) or six (n = 1 536) steps over two parts, so a
+    part takes a second and, at 1 536, a third step (q >= S) with its sums carried across
+    the steps it skips. The build's constant (asserted against the build in
+    test_planner_and_model_agree) wraps from n = 2 818 on, which the model cannot
+    afford; the GPU tests of tests/test_gpu_poly_scale.py run the kernel there."""
+    consts = plans[0]
+    assert consts["tree_split"] == tm.TREE_SPLIT == 8  # the default stays the build's
+    split = 2
+    wrapped = [(l, max(tm.tree_steps(n, l), default=0), tm.tree_split(l, split)) for l, *_ in tm.tree_plan(n)]
+    assert max(steps for _, steps, _ in wrapped) == (4 if n == 1025 else 6)
+    rounds = 1 if n == 1025 else 2  # every part takes a second step; at 1 536 a third one too
+    assert any(steps > rounds * parts and parts == split for _, steps, parts in wrapped)
+    assert all(steps <= tm.tree_split(l) for l, steps, _ in wrapped)  # the build's constant never wraps here
+    assert tm.tree_most_steps(2817)[0] == 8 and tm.tree_most_steps(2818) == (9, 11, 8)  # the first n that does
+    field = 1
+    p = po.MODULI[field]
+    pts = _points(field, n, seed=31)
+    want = list(_fast(field, n, 31))
+    # 1 025 over three blocks along x: the wrapped deal and the x loop's further trips meet in one block
+    assert tm.interpolate(p, pts, num_cus=8, grid_x=3 if n == 1025 else None, split=split) == want
+
+
+@pytest.mark.parametrize("n,plan", [(513, (2, 512)), (1281, (1, 1536))])
+def test_weights_model_several_trips_per_part(n, plan):
+    """k_poly_weights with part_len > 256: a part's j0 loop takes a second trip
+    (two parts of 512 at n = 513 on one CU, the second one short; one part of
+    six trips at n = 1 281), the LDS stage refilled inside one part and the
+    j = i skip landing in a later trip. With y = 1 leaf i holds 1 / d_i: checked
+    against d_i = prod_{j != i} (x_i - x_j) at lanes of every trip."""
+    field, num_cus = 2, 1
+    p = po.MODULI[field]
+    assert tm.weights_plan(n, num_cus) == plan and plan[1] > tm.BLOCK
+    assert all(tm.weights_plan(k, num_cus)[1] == tm.BLOCK for k in range(1, 513))  # 513 is the smallest such n
+    xs = [x for x, _ in _points(field, n, seed=31)]
+    M, N, dup = tm.leaves(p, xs, [1] * n, num_cus)
+    assert dup == 0 and M == [(-x) % p for x in xs]
+    for i in (0, 255, 256, 300, 511, 512, n - 1):
+        d_i = 1
+        for j, xj in enumerate(xs):
+            if j != i:
+                d_i = d_i * (xs[i] - xj) % p
+        assert N[i] * d_i % p == 1, i
