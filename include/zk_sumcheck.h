@@ -680,6 +680,126 @@ int zk_r1cs_verify(zk_r1cs* r, zk_repr repr, const zk_fe* io, const zk_fe* coeff
                    zk_transcript* transcript, int* out_verified, zk_fe* out_rx /* sx */, zk_fe* out_ry /* sy */);
 
 /* ---------------------------------------------------------------------------
+ * Lookups (LogUp, Haboeck 2022) over committed columns: every
+ * entry of a committed column lies in a public table. Range checks, byte
+ * decompositions and fixed function tables reduce to it. The two device
+ * primitives in front of it, the batched inversion and the multiplicity
+ * count, take any field; proving and verifying are BLS12-381 Fr, as all KZG
+ * here.
+ *
+ * The statement. f: a column of 2^n elements, 1 <= n <= 24 (ZK_EUNSUPPORTED
+ * above). t: a public table of T elements, 1 <= T <= 2^n, duplicates allowed.
+ * Claim: every f_i equals some t_j. t_pad[j] = t[min(j, T - 1)] for j < 2^n.
+ * m_j = #{i : f_i = t_j} at the FIRST index j holding that value, 0 at every
+ * later duplicate and at the padding. h_f = 1 / (alpha - f), h_t = m /
+ * (alpha - t_pad).
+ *
+ * The transcript, on the caller's handle:
+ *   1. digest = Keccak-256 of: the ASCII bytes "zk-lookup-v1"; then as u32
+ *      little-endian field, T; then each t_j as its 32 canonical little-endian
+ *      bytes. Computed at handle creation;
+ *   2. append(digest), append(u32 little-endian n), then the 96 bytes of the
+ *      commitment of f and of m (the committed sum-check's encoding);
+ *   3. alpha = get_random_challenge;
+ *   4. the helper columns h_f and h_t (1 / 0 is taken as 0: then identity (b)
+ *      or (c) below fails and the proof is rejected);
+ *   5. the 96 bytes of the commitment of h_f and of h_t;
+ *   6. tau_0 .. tau_(n-1) by n consecutive get_random_challenge, then lambda =
+ *      get_random_challenge;
+ *   7. one zk_dev_committed_sumcheck_prove, unchanged, with the four
+ *      commitments as commitments_in (it absorbs them again, in table order),
+ *      claimed sum 0, degree 3, committed mask 0b1111, the eleven tables
+ *        0 h_f   1 h_t   2 f   3 m   4 t_pad   5 ones   6 -ones
+ *        7 alpha lambda eq(tau,.)     8 -lambda eq(tau,.)
+ *        9 alpha lambda^2 eq(tau,.)   10 -lambda^2 eq(tau,.)
+ *      and the eight terms {0,5,5} {1,6,5} {7,0,5} {8,0,2} {8,5,5} {9,1,5}
+ *      {10,1,4} {10,3,5}: the sum is
+ *        (a) sum (h_f - h_t)
+ *        (b) + lambda   sum eq(tau,.) (h_f (alpha - f) - 1)
+ *        (c) + lambda^2 sum eq(tau,.) (h_t (alpha - t_pad) - m).
+ * A proof: coeffs[4 n] / ncoeffs[n] (the round polynomials, 4 slots per round,
+ * zero past the trimmed count), table_evals[11], four commitments in table
+ * order (h_f, h_t, f, m) and n quotient commitments.
+ *
+ *   zk_fe_batch_inverse / zk_dev_fe_batch_inverse   out[i] = in[i]^-1, and 0 -> 0,
+ *                   over count >= 1 elements (any count, not only a power of
+ *                   two): Montgomery's trick, one Fermat power per 64
+ *                   elements. The host entry takes zk_fe arrays in `repr`; the
+ *                   device entry Montgomery tables on the device. out == in is
+ *                   allowed; a partial overlap is ZK_EINVAL.
+ *   zk_lookup_new   validates the table (a value >= p, T = 0: ZK_EINVAL; T >
+ *                   2^24: ZK_EUNSUPPORTED) and builds its hash on the host,
+ *                   deterministically: 2^s slots, the power of two at least
+ *                   2 T; slot of a value = ((low 32 bits of its canonical
+ *                   form) * 0x9E3779B1 mod 2^32) >> (32 - s), so values equal
+ *                   mod 2^32 collide; linear probing in index order; a slot
+ *                   holds the first index of its value, or 0xFFFFFFFF when
+ *                   empty. With a context the slots and the Montgomery table
+ *                   go to the device and the handle works through that
+ *                   context: use it only while the context lives
+ *                   (zk_lookup_free itself does not read the context). With
+ *                   ctx == NULL the handle is host-only: it counts, evaluates
+ *                   and verifies on the host, but cannot prove (ZK_EDEVICE).
+ *   zk_lookup_info  T, the slot count, the digest and the slots; any output
+ *                   may be NULL.
+ *   zk_lookup_multiplicities / zk_dev_lookup_multiplicities   m over all 2^n
+ *                   slots (zero at or above T) from `count` column entries, 1
+ *                   <= count <= 2^24, T <= 2^n; *out_missing = the number of
+ *                   entries found nowhere in the table. The device entry takes
+ *                   and fills Montgomery tables on the device that do not
+ *                   overlap; a host-only handle counts on the host.
+ *   zk_lookup_table_eval   t_pad~(point[n]) in O(T) products on the host:
+ *                   c + sum_(j<T) (t_j - c) eq(point, j), c = t[T - 1].
+ *   zk_lookup_prove / zk_dev_lookup_prove   f: 2^n entries in host / device
+ *                   (Montgomery) memory, only read. kzg: a setup of n
+ *                   variables. commitment_in (NULL: compute it) is f's
+ *                   commitment, absorbed and returned as given, only checked to
+ *                   be on the curve. Writes the proof, out_point[n] (the
+ *                   sum-check's challenges) and *out_missing. A column with
+ *                   non-members is not refused: out_missing reports them, and
+ *                   the proof is rejected.
+ *   zk_lookup_verify   works with a host-only handle. Replays steps 2 - 6,
+ *                   calls zk_committed_sumcheck_verify, then checks the public
+ *                   entries of table_evals itself: ones is 1, -ones is -1, the
+ *                   four scaled eq entries by eq(tau, point), t_pad by the
+ *                   handle. A rejection is ZK_OK with *out_verified = 0 and
+ *                   nothing else written, the transcript included.
+ *                   SOUNDNESS: the note on g2_taus at zk_gkr_circuit_verify_kzg
+ *                   applies unchanged: they must come from a setup the
+ *                   verifier trusts, not from the prover.
+ * ZK_EINVAL: a null pointer, T = 0, T > 2^n, n = 0, a value >= p, a setup whose
+ * variable count is not n, a field other than BLS12-381 Fr for prove or
+ * verify, a point not on the curve. ZK_EUNSUPPORTED: n > 24. Every call works
+ * on a copy of the transcript and hands it back only on success: nothing is
+ * written on failure.
+ * ------------------------------------------------------------------------- */
+typedef struct zk_lookup zk_lookup;
+int zk_fe_batch_inverse(zk_field field, zk_repr repr, const zk_fe* in, uint64_t count, zk_fe* out);
+int zk_dev_fe_batch_inverse(zk_ctx* ctx, zk_field field, const void* d_in, uint64_t count, void* d_out);
+int zk_lookup_new(zk_ctx* ctx /* NULL: host-only */, zk_field field, zk_repr repr, const zk_fe* table, uint32_t T,
+                  zk_lookup** out);
+void zk_lookup_free(zk_lookup* lk);
+int zk_lookup_info(const zk_lookup* lk, uint32_t* out_T, uint32_t* out_nslots, uint8_t out_digest[32],
+                   uint32_t* out_slots /* nslots */);
+int zk_lookup_multiplicities(zk_lookup* lk, zk_repr repr, const zk_fe* f, uint64_t count, uint32_t n,
+                             zk_fe* out_m /* 2^n */, uint64_t* out_missing);
+int zk_dev_lookup_multiplicities(zk_lookup* lk, const void* d_f, uint64_t count, void* d_m /* 2^n */, uint32_t n,
+                                 uint64_t* out_missing);
+int zk_lookup_table_eval(zk_lookup* lk, zk_repr repr, const zk_fe* point /* n */, uint32_t n, zk_fe* out);
+int zk_lookup_prove(zk_lookup* lk, zk_repr repr, const zk_fe* f /* 2^n */, uint32_t n, const zk_kzg* kzg,
+                    const zk_g1* commitment_in /* NULL: compute it */, zk_transcript* transcript,
+                    zk_fe* out_coeffs /* 4 n */, uint8_t* out_ncoeffs /* n */, zk_fe* out_table_evals /* 11 */,
+                    zk_fe* out_point /* n */, zk_g1* out_commitments /* 4 */, zk_g1* out_opening /* n */,
+                    uint64_t* out_missing);
+int zk_dev_lookup_prove(zk_lookup* lk, zk_repr repr, const void* d_f, uint32_t n, const zk_kzg* kzg,
+                        const zk_g1* commitment_in, zk_transcript* transcript, zk_fe* out_coeffs, uint8_t* out_ncoeffs,
+                        zk_fe* out_table_evals, zk_fe* out_point, zk_g1* out_commitments, zk_g1* out_opening,
+                        uint64_t* out_missing);
+int zk_lookup_verify(zk_lookup* lk, zk_repr repr, uint32_t n, const zk_fe* coeffs, const uint8_t* ncoeffs,
+                     const zk_fe* table_evals /* 11 */, const zk_g1* commitments /* 4 */, const zk_g1* opening /* n */,
+                     const zk_g2* g2_taus, zk_transcript* transcript, int* out_verified, zk_fe* out_point /* n */);
+
+/* ---------------------------------------------------------------------------
  * Proof blob: a canonical byte form of a proof, so a proof
  * produced on the CPU, on one GPU or on G GPUs can be compared as one digest
  * and shipped/verified elsewhere. The reference keeps proofs as in-memory

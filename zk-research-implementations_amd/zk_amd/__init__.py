@@ -8,6 +8,7 @@ Python mirror of the reference crates' API (obah/zk-research-implementations):
   gkr_prove / gkr_verify over every product and factor of a SumPoly: composed_prove, composed_verify, composed_combine
   the same with the tables KZG-committed and opened at once: committed_prove, committed_verify (zk_amd.committed)
   R1CS satisfiability over a committed witness: R1CS, R1csProof (zk_amd.r1cs)
+  lookups (LogUp) over a committed column, batched field inversion: Lookup, LookupProof, batch_inverse (zk_amd.lookup)
   merkle_tree::{MerkleTree, MerkleProof, ProofData, LeafSide}  (zk_amd.merkle)
   fft::{fft_evaluate, fft_interpolate, split_poly, get_interpolation_roots}  (zk_amd.fft)
   univariate_polynomial::UnivariatePoly::{interpolate, evaluate} over many points  (zk_amd.poly)
@@ -63,4 +64,5 @@ from . import poly  # noqa: F401  (interpolation and batch evaluation over arbit
 from . import shamir  # noqa: F401  (shamir_secret_sharing crate mirror)
 from .committed import CommittedProof, CommittedVerify, committed_prove, committed_verify  # noqa: F401
 from .r1cs import R1CS, R1csProof, R1csVerify  # noqa: F401
+from .lookup import Lookup, LookupProof, LookupVerify, batch_inverse  # noqa: F401
 from ._lib import ZkError  # noqa: F401

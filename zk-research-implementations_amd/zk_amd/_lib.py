@@ -112,6 +112,17 @@ SIGNATURES = {
     "zk_r1cs_prove": (I, [P, I, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
     "zk_dev_r1cs_prove": (I, [P, I, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
     "zk_r1cs_verify": (I, [P, I, P, P, P, P, P, P, P, P, P, P, C.POINTER(C.c_int), P, P]),
+    "zk_fe_batch_inverse": (I, [I, I, P, U64, P]),
+    "zk_dev_fe_batch_inverse": (I, [P, I, P, U64, P]),
+    "zk_lookup_new": (I, [P, I, I, P, U32, C.POINTER(C.c_void_p)]),
+    "zk_lookup_free": (None, [P]),
+    "zk_lookup_info": (I, [P, C.POINTER(U32), C.POINTER(U32), P, P]),
+    "zk_lookup_multiplicities": (I, [P, I, P, U64, U32, P, C.POINTER(U64)]),
+    "zk_dev_lookup_multiplicities": (I, [P, P, U64, P, U32, C.POINTER(U64)]),
+    "zk_lookup_table_eval": (I, [P, I, P, U32, P]),
+    "zk_lookup_prove": (I, [P, I, P, U32, P, P, P, P, P, P, P, P, P, C.POINTER(U64)]),
+    "zk_dev_lookup_prove": (I, [P, I, P, U32, P, P, P, P, P, P, P, P, P, C.POINTER(U64)]),
+    "zk_lookup_verify": (I, [P, I, U32, P, P, P, P, P, P, P, C.POINTER(C.c_int), P]),
     "zk_kzg_setup": (I, [P, I, P, U32, C.POINTER(C.c_void_p)]),
     "zk_kzg_free": (None, [P]),
     "zk_kzg_lagrange_basis": (I, [P, P, U32, P]),
