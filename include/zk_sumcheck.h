@@ -206,6 +206,10 @@ int zk_gkr_sumcheck_verify(zk_field field, zk_repr repr, const zk_fe* coeffs /* 
  *   out_output_poly[2], out_coeffs[3*total] + out_ncoeffs[total] (trimmed),
  *   out_challenges[total], out_claims[2*(nlayers-1)] = (o1, o2) per layer
  *   except the input layer, out_input_evals[2].
+ * ZK_EINVAL, with no output written: a null pointer (out_claims may be NULL
+ * when nlayers = 1), nlayers = 0 or > 24, an unsupported shape, ninputs !=
+ * 2 gates[0], an op > 1, an input >= p in either representation, an unknown
+ * field or repr.
  * ------------------------------------------------------------------------- */
 int zk_gkr_circuit_rounds(uint32_t nlayers, const uint32_t* gates, uint32_t* out_total_rounds);
 int zk_gkr_circuit_prove(zk_ctx* ctx, zk_field field, zk_repr repr, uint32_t nlayers, const uint32_t* gates,

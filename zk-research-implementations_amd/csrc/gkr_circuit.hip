@@ -34,6 +34,8 @@ void check_shape(uint32_t nlayers, const uint32_t* gates) {
   require(lg2u(2 * (uint64_t)gates[0]) <= 14, "circuit too large (input layer tables of (2 G_0)^2 entries)");
 }
 
+void check_repr(zk_repr repr) { require(repr == ZK_REPR_CANONICAL || repr == ZK_REPR_MONTGOMERY, "unknown repr"); }
+
 void check_circuit(uint32_t nlayers, const uint32_t* gates, const uint8_t* ops, uint32_t ninputs) {
   check_shape(nlayers, gates);
   require(ops != nullptr, "null argument");
@@ -472,6 +474,7 @@ int zk_gkr_circuit_prove(zk_ctx* c, zk_field field, zk_repr repr, uint32_t nlaye
   return guarded([&] {
     require(c && inputs && out_output_poly && out_coeffs && out_ncoeffs && out_challenges && out_input_evals,
             "null argument");
+    check_repr(repr);
     check_circuit(nlayers, gates, ops, ninputs);
     require(nlayers == 1 || out_claims, "null argument");
     bind(c);
@@ -492,6 +495,7 @@ int zk_gkr_circuit_verify(zk_field field, zk_repr repr, uint32_t nlayers, const 
                           const uint8_t* ncoeffs, const zk_fe* claims, const zk_fe* input_evals, int* out_verified) {
   return guarded([&] {
     require(output_poly && coeffs && ncoeffs && input_evals && out_verified, "null argument");
+    check_repr(repr);
     check_circuit(nlayers, gates, ops, ninputs);
     require(nlayers == 1 || claims, "null argument");
     dispatch(field, [&](auto f) {
