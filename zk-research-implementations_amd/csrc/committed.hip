@@ -4,7 +4,7 @@
 // copied), rho drawn after the tables' evaluations, one batched opening
 // (kzg.hip) — in the order committed_plan.hpp fixes. Also the two table builders
 // a zero-check needs in public: the linear combination (committed.hpp) and the
-// eq table (wired.hip's eq_table_device).
+// eq table (host.hpp eq_table_device).
 #include "host.hpp"
 #include "committed.hpp"
 
@@ -14,19 +14,7 @@ namespace {
 using Fr381 = zk::Bls12_381Fr;
 constexpr zk_field kField = ZK_BLS12_381_FR;  // all KZG here is over BLS12-381
 
-void check_repr(zk_repr repr) { require(repr == ZK_REPR_CANONICAL || repr == ZK_REPR_MONTGOMERY, "unknown repr"); }
-
-// an inner C-ABI call's failure, passed on with its message
-void pass_on(int rc) {
-  if (rc != ZK_OK) {
-    const std::string msg = g_last_error;
-    fail(rc, msg);
-  }
-}
-
-void plan_check(int rc, const char* err) {
-  if (rc != zkc::C_OK) fail(rc == zkc::C_EUNSUPPORTED ? ZK_EUNSUPPORTED : ZK_EINVAL, err);
-}
+constexpr auto plan_check = plan_check_with<zkc::C_OK, zkc::C_EUNSUPPORTED>;
 
 struct ProveArgs {
   uint32_t ntables, nvars, nterms, degree, mask;

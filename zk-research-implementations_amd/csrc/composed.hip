@@ -13,9 +13,7 @@ using namespace zkh;
 static_assert(ZK_COMPOSED_MAX_DEGREE == zkc::kComposedMaxDegree, "the header states the cap");
 
 namespace {
-void plan_check(int rc, const char* err) {
-  if (rc != zkc::C_OK) fail(rc == zkc::C_EUNSUPPORTED ? ZK_EUNSUPPORTED : ZK_EINVAL, err);
-}
+constexpr auto plan_check = plan_check_with<zkc::C_OK, zkc::C_EUNSUPPORTED>;
 
 struct Shape {
   uint32_t ntables, nvars, nterms, degree;

@@ -229,26 +229,49 @@ inline void composed_out_init(ComposedOut& o, uint32_t nvars, uint32_t degree, c
   o.challenges.assign(nvars, zero);
 }
 
-// gkr_verify (sum_check_protocol.rs:117-150) with a degree bound. cf: (degree + 1)
-// Montgomery coefficients per round. A round with more than degree + 1
-// coefficients, or with s(0) + s(1) != claim, rejects: false, and the caller
-// reports final claim 0 and one zero challenge.
-template <class F>
-bool composed_verify(uint32_t degree, const Fe* cf, const uint8_t* ncoeffs, uint32_t nrounds, Fe claim,
-                     zk_transcript* tr, Fe& final_claim, std::vector<Fe>& challenges) {
+// gkr_verify (sum_check_protocol.rs:117-150) with a degree bound, the one
+// round verifier of every sum-check here. coef(k, i) gives coefficient i of
+// round k as a Montgomery image; it is asked round by round, only for the
+// rounds reached and the coefficients counted, so a caller may convert and
+// validate there. Per round: s(0) + s(1) against the claim, the coefficients
+// absorbed, r_k drawn and appended to `challenges`, the claim moved to s(r_k).
+// Says where it stopped: at nrounds having passed every round, or at the first
+// round with more than degree + 1 coefficients or the wrong sum (claim and
+// challenges as they stood before that round).
+enum class RoundStop { passed, too_many_coeffs, wrong_sum };
+struct RoundsEnd {
+  RoundStop why;
+  uint32_t round;
+};
+template <class F, class Coef>
+RoundsEnd verify_rounds(uint32_t degree, const uint8_t* ncoeffs, uint32_t nrounds, Coef&& coef, zk_transcript* tr,
+                        Fe& claim, std::vector<Fe>& challenges) {
   using namespace zk;
-  challenges.clear();
   for (uint32_t k = 0; k < nrounds; ++k) {
     const int m = ncoeffs[k];
-    if (m > (int)degree + 1) return false;
-    const Fe* c = cf + (size_t)(degree + 1) * k;
+    if (m > (int)degree + 1) return {RoundStop::too_many_coeffs, k};
+    Fe c[kComposedMaxDegree + 1];
+    for (int i = 0; i < m; ++i) c[i] = coef(k, (uint32_t)i);
     const Fe s01 = hfe_add<F>(composed_eval<F>(c, m, fe_zero<F>()), composed_eval<F>(c, m, fe_one<F>()));
-    if (!fe_eq<F>(s01, claim)) return false;
+    if (!fe_eq<F>(s01, claim)) return {RoundStop::wrong_sum, k};
     zkh::absorb<F>(tr, c, (size_t)m);
     const Fe r = zkh::challenge<F>(tr);
     challenges.push_back(r);
     claim = composed_eval<F>(c, m, r);
   }
+  return {RoundStop::passed, nrounds};
+}
+
+// The rounds of a composed sum-check. cf: (degree + 1) Montgomery coefficients
+// per round. A round with more than degree + 1 coefficients, or with
+// s(0) + s(1) != claim, rejects: false, and the caller reports final claim 0
+// and one zero challenge.
+template <class F>
+bool composed_verify(uint32_t degree, const Fe* cf, const uint8_t* ncoeffs, uint32_t nrounds, Fe claim,
+                     zk_transcript* tr, Fe& final_claim, std::vector<Fe>& challenges) {
+  challenges.clear();
+  auto coef = [&](uint32_t k, uint32_t i) { return cf[(size_t)(degree + 1) * k + i]; };
+  if (verify_rounds<F>(degree, ncoeffs, nrounds, coef, tr, claim, challenges).why != RoundStop::passed) return false;
   final_claim = claim;
   return true;
 }

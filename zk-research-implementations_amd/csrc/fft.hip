@@ -186,15 +186,11 @@ void run_fft(zk_ctx* c, const Fe* d_in, uint32_t m, bool inverse, Fe* d_out) {
   }
 }
 
-void check_repr(zk_repr repr) {
-  require(repr == ZK_REPR_CANONICAL || repr == ZK_REPR_MONTGOMERY, "unknown representation");
-}
-
 // fft_evaluate :31-41 / fft_interpolate :43-60 over host values
 int host_transform(zk_ctx* c, zk_field field, zk_repr repr, const zk_fe* in, uint64_t n, zk_fe* out, bool inverse) {
   return guarded([&] {
     require(c && in && out, "null argument");
-    check_repr(repr);
+    check_repr(repr, "unknown representation");
     dispatch(field, [&](auto f) {
       using F = decltype(f);
       const uint32_t m = transform_log<F>(n);
@@ -215,7 +211,7 @@ extern "C" {
 int zk_fft_root_of_unity(zk_field field, zk_repr repr, uint64_t n, zk_fe* out) {
   return guarded([&] {
     require(out != nullptr, "null argument");
-    check_repr(repr);
+    check_repr(repr, "unknown representation");
     dispatch(field, [&](auto f) {
       using F = decltype(f);
       *out = out_repr<F>(repr, h_root<F>(transform_log<F>(n)));
@@ -226,7 +222,7 @@ int zk_fft_root_of_unity(zk_field field, zk_repr repr, uint64_t n, zk_fe* out) {
 int zk_fft_interpolation_roots(zk_field field, zk_repr repr, uint64_t n, zk_fe* out) {
   return guarded([&] {
     require(out != nullptr, "null argument");
-    check_repr(repr);
+    check_repr(repr, "unknown representation");
     require(n >= 1 && n <= ((uint64_t)1 << kFftMaxLog), "no evaluation domain of this size");
     dispatch(field, [&](auto f) {
       using F = decltype(f);
@@ -269,7 +265,7 @@ int zk_poly_mul(zk_ctx* c, zk_field field, zk_repr repr, const zk_fe* a, uint64_
                 zk_fe* out, uint64_t cap, uint64_t* out_len) {
   return guarded([&] {
     require(c && a && b && out_len, "null argument");
-    check_repr(repr);
+    check_repr(repr, "unknown representation");
     if (na > ((uint64_t)1 << kFftMaxLog) || nb > ((uint64_t)1 << kFftMaxLog))
       fail(ZK_EUNSUPPORTED, "products above 2^28 terms are not supported");
     while (na > 0 && fe_all_zero(a[na - 1])) --na;  // degree() :28-32

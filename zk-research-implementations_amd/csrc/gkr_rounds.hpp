@@ -126,8 +126,8 @@ void host_round_sums(const std::vector<Fe> (&T)[4], Fe& e0, Fe& e2, Fe* e1 = nul
   e2 = wide_to_fe<F>(a2);
 }
 
-// One phase of a circuit layer's sum-check entirely on the host (the tree
-// prover's host_layer in gkr_circuit.hip, the wired prover's in wired.hip): n
+// One phase of a circuit layer's sum-check entirely on the host (host_layer in
+// gkr_layers.hpp, for the tree prover and the wired prover alike): n
 // rounds over the four tables T, starting at global round k0.
 template <class F>
 void host_layer_phase(std::vector<Fe> (&T)[4], uint32_t n, uint32_t k0, zk_transcript* tr, GkrOut& out) {

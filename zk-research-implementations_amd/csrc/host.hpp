@@ -1,7 +1,7 @@
-// Host-side core shared by the library's translation units (zk_sumcheck.hip,
-// gkr_circuit.hip, kzg.hip, blob.hip): errors and the C-ABI guard, field
-// dispatch and representation conversion, the device context
-// (zk_ctx), kernel launch / timing, and the sum-check / GKR round drivers.
+// Host-side core shared by the library's translation units: errors and the
+// C-ABI guard, the drivers' small helpers, field dispatch and representation
+// conversion, the device context (zk_ctx), kernel launch / timing, and the
+// sum-check / GKR round drivers.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -23,6 +23,7 @@
 #include "keccak.hpp"
 #include "kernels.hpp"
 #include "mfma.hpp"
+#include "wired.hpp"
 #include "gkr_plan.hpp"
 #include "gkr_rounds.hpp"
 #include "fft_plan.hpp"
@@ -74,6 +75,26 @@ int guarded(Fn&& fn) {
 
 inline void require(bool cond, const char* msg) {
   if (!cond) fail(ZK_EINVAL, msg);
+}
+inline void check_repr(zk_repr repr, const char* msg = "unknown repr") {
+  require(repr == ZK_REPR_CANONICAL || repr == ZK_REPR_MONTGOMERY, msg);
+}
+// an inner C-ABI call's failure, passed on with its message
+inline void pass_on(int rc) {
+  if (rc != ZK_OK) {
+    const std::string msg = g_last_error;
+    fail(rc, msg);
+  }
+}
+// a *_plan.hpp validator's answer (its own OK / EUNSUPPORTED values, anything else invalid) as the library's error
+template <int OK, int EUNSUPPORTED>
+void plan_check_with(int rc, const char* err) {
+  if (rc != OK) fail(rc == EUNSUPPORTED ? ZK_EUNSUPPORTED : ZK_EINVAL, err);
+}
+// two ranges of `bytes` bytes share a byte
+inline bool overlap(const void* a, const void* b, uint64_t bytes) {
+  const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+  return x < y + bytes && y < x + bytes;
 }
 
 // runtime field -> compile-time parameter set
@@ -146,6 +167,32 @@ struct ScopedBuf {
   ScopedBuf(const ScopedBuf&) = delete;
   ScopedBuf& operator=(const ScopedBuf&) = delete;
   ~ScopedBuf() { b.release(); }
+};
+inline uint32_t blocks_for(uint64_t n) { return (uint32_t)((n + zk::kBlock - 1) / zk::kBlock); }
+template <class T>
+void to_device(DevBuf& b, const std::vector<T>& v) {
+  b.ensure(std::max<size_t>(v.size() * sizeof(T), 16));
+  if (!v.empty()) HIPCK(hipMemcpy(b.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+}
+// One grouping of gates or matrix entries by row on the device (wired_plan.hpp
+// WiredCsr): `other` is what each entry reads besides its row (a wired gate's
+// second wire with its op in the top bit, an R1CS entry's column or row);
+// `gate`, the entries' own order, is loaded only where a kernel reads it.
+struct DevCsr {
+  DevBuf gate, other, chunks, split;
+  uint32_t nchunks = 0, nsingle = 0, nsplit = 0, nslots = 0;
+  void load(const zkw::WiredCsr& c, const std::vector<uint32_t>& oth) {
+    to_device(other, oth);
+    to_device(chunks, c.chunks);
+    to_device(split, c.split);
+    nchunks = (uint32_t)c.chunks.size();
+    nsingle = c.nsingle;
+    nsplit = (uint32_t)c.split.size();
+    nslots = nchunks - nsingle;
+  }
+  void release() {
+    for (DevBuf* b : {&gate, &other, &chunks, &split}) b->release();
+  }
 };
 
 // The twiddle tables of one transform shape (fft.hip), built on the host once
@@ -290,10 +337,6 @@ static_assert(6656 + sizeof(zk::RPost) <= 8192 && 6144 + sizeof(zk::RPost) <= kH
 
 inline void bind(zk_ctx* c) { HIPCK(hipSetDevice(c->device)); }
 void wired_release_all(zk_ctx* c);  // wired.hip: frees c->wired (zk_ctx_destroy)
-// wired.hip (k_eq_table): eq(pt[0..n), .), MSB first as host_eq_table, into dst
-// (2^n entries, n >= 1); tmp holds the tables between passes (2^(n-2) + 8 entries)
-template <class F>
-void eq_table_device(zk_ctx* c, const Fe* pt, uint32_t n, Fe* dst, Fe* tmp);
 uint32_t kzg_nvars(const zk_kzg* k);  // kzg.hip: a setup's variable count
 void check_g1_points(const zk_g1* pts, uint32_t n);  // kzg.hip: ZK_EINVAL unless canonical and on the curve ((0, 0) = infinity)
 
@@ -1594,7 +1637,59 @@ std::vector<uint8_t> table_bytes_from_device(zk_ctx* c, const Fe* dev, size_t n)
   return b;
 }
 
+// eq(pt[0..n), .), MSB first as host_eq_table, into dst (2^n entries, n >= 1), by doubling
+// in passes of <= 3 coordinates (wired.hpp k_eq_table); the tables between passes live in
+// tmp (< 2^(n-2) + 8 entries in all)
+template <class F>
+void eq_table_device(zk_ctx* c, const Fe* pt, uint32_t n, Fe* dst, Fe* tmp) {
+  const Fe* src = nullptr;
+  uint32_t have = 0;
+  size_t off = 0;
+  while (have < n) {
+    const uint32_t S = have == 0 && n % 3 ? n % 3 : 3;
+    Fe* out = have + S == n ? dst : tmp + off;
+    const uint32_t nsrc = 1u << have;
+    zk::EqPts p{};
+    for (uint32_t k = 0; k < S; ++k) p.r[k] = pt[have + k];
+    const double made = (double)nsrc * (1u << S);
+    auto go = [&](auto kern) { launch(c, ZK_K_LAYER, 32.0 * (nsrc + made), made, kern, blocks_for(nsrc), src, nsrc, p, out); };
+    if (S == 1) go(zk::k_eq_table<F, 1>);
+    else if (S == 2) go(zk::k_eq_table<F, 2>);
+    else go(zk::k_eq_table<F, 3>);
+    if (out != dst) off += (size_t)1 << (have + S);
+    src = out;
+    have += S;
+  }
+}
+
+// sum_j w[j] e[j] over n entries on the device (k_wired_dot), the blocks' parts (<= 64,
+// in `parts`) added here
+template <class F>
+Fe dot_device(zk_ctx* c, const DevBuf& parts, const Fe* w, const Fe* e, uint64_t n) {
+  const uint32_t grid = (uint32_t)std::min<uint64_t>(blocks_for(n), 64);
+  launch(c, ZK_K_LAYER, 64.0 * n, (double)n, zk::k_wired_dot<F>, grid, w, e, n, parts.fe());
+  Fe part[64];
+  HIPCK(hipMemcpyAsync(part, parts.fe(), grid * sizeof(Fe), hipMemcpyDeviceToHost, c->stream));
+  sync(c);
+  Fe s = zk::fe_zero<F>();
+  for (uint32_t i = 0; i < grid; ++i) s = zk::hfe_add<F>(s, part[i]);
+  return s;
+}
+
 inline bool pow2_ok(uint32_t nvars) { return nvars < 40; }
+
+// gkr_verify (sum_check_protocol.rs:117-150) over rounds k0 .. k0 + n - 1 of a proof as
+// the C ABI passes it: 3 coefficients per round in `repr`, converted and validated as
+// each round is reached (zkc::verify_rounds). False when a round's sum is wrong;
+// ZK_EINVAL when a round that is reached has more than 3 coefficients.
+template <class F>
+bool gkr_verify_rounds(zk_repr repr, const zk_fe* coeffs, const uint8_t* ncoeffs, size_t k0, uint32_t n,
+                       zk_transcript* tr, Fe& claim, std::vector<Fe>& chal) {
+  auto coef = [&](uint32_t k, uint32_t i) { return in_mont<F>(repr, coeffs[3 * (k0 + k) + i]); };
+  const zkc::RoundsEnd end = zkc::verify_rounds<F>(2, ncoeffs + k0, n, coef, tr, claim, chal);
+  require(end.why != zkc::RoundStop::too_many_coeffs, "round polynomial has more than 3 coefficients");
+  return end.why == zkc::RoundStop::passed;
+}
 
 template <class F>
 void emit_gkr(zk_repr repr, const GkrOut& g, uint32_t n, zk_fe* out_coeffs, uint8_t* out_ncoeffs,

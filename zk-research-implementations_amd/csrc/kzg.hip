@@ -57,7 +57,7 @@ void scan_u32(zk_ctx* c, uint32_t* a, uint64_t n, int depth = 0) {
          (const uint32_t*)dptr<uint32_t>(sums));
 }
 
-uint32_t blocks_for(uint64_t n) { return (uint32_t)std::max<uint64_t>(1, (n + zk::kBlock - 1) / zk::kBlock); }
+uint32_t blocks1_for(uint64_t n) { return std::max(1u, blocks_for(n)); }  // never an empty grid
 
 // Sum each segment s = items [off[s], off[s+1]) (device u32 offsets, nseg + 1).
 // Level 0 reads affine bases[order[j]] (order != null) or Jacobian items0[j].
@@ -77,24 +77,24 @@ G1J* seg_reduce(zk_ctx* c, const G1A* bases, uint64_t nbases, const uint32_t* or
     DevBuf& part = c->msm[pool + 3 + flip];
     toff.ensure((nseg + 1) * 4);
     uint32_t* to = dptr<uint32_t>(toff);
-    launch(c, ZK_K_MSM, 12.0 * nseg, 0, zk::k_seg_task_counts, blocks_for(nseg), cur_off, nseg, task, to);
+    launch(c, ZK_K_MSM, 12.0 * nseg, 0, zk::k_seg_task_counts, blocks1_for(nseg), cur_off, nseg, task, to);
     HIPCK(hipMemsetAsync(to + nseg, 0, 4, c->stream));
     scan_u32(c, to, nseg + 1);
     uint32_t total = 0;
     HIPCK(hipMemcpyAsync(&total, to + nseg, 4, hipMemcpyDeviceToHost, c->stream));
     sync(c);
     tseg.ensure((size_t)total * 4);
-    launch(c, ZK_K_MSM, 4.0 * total, 0, zk::k_seg_task_owner, blocks_for(nseg), (const uint32_t*)to, nseg, total,
+    launch(c, ZK_K_MSM, 4.0 * total, 0, zk::k_seg_task_owner, blocks1_for(nseg), (const uint32_t*)to, nseg, total,
            dptr<uint32_t>(tseg));
     part.ensure((size_t)total * sizeof(G1J));
     if (xyzz)
-      launch(c, ZK_K_MSM, 0, 0, zk::k_seg_sum_xyzz, blocks_for(total), xitems0, cur_off, (const uint32_t*)to,
+      launch(c, ZK_K_MSM, 0, 0, zk::k_seg_sum_xyzz, blocks1_for(total), xitems0, cur_off, (const uint32_t*)to,
              (const uint32_t*)dptr<uint32_t>(tseg), total, task, dptr<G1J>(part));
     else if (gather)
-      launch(c, ZK_K_MSM, 0, 0, zk::k_seg_sum<true>, blocks_for(total), bases, nbases, order, (const G1J*)nullptr, cur_off,
+      launch(c, ZK_K_MSM, 0, 0, zk::k_seg_sum<true>, blocks1_for(total), bases, nbases, order, (const G1J*)nullptr, cur_off,
              (const uint32_t*)to, (const uint32_t*)dptr<uint32_t>(tseg), total, task, dptr<G1J>(part));
     else
-      launch(c, ZK_K_MSM, 0, 0, zk::k_seg_sum<false>, blocks_for(total), (const G1A*)nullptr, (uint64_t)0,
+      launch(c, ZK_K_MSM, 0, 0, zk::k_seg_sum<false>, blocks1_for(total), (const G1A*)nullptr, (uint64_t)0,
              (const uint32_t*)nullptr, items, cur_off, (const uint32_t*)to, (const uint32_t*)dptr<uint32_t>(tseg),
              total, task, dptr<G1J>(part));
     if (total == nseg) return dptr<G1J>(part);
@@ -241,7 +241,7 @@ std::vector<G1J> msm_window_sums(zk_ctx* c, const G1A* bases, const Fe* scalars,
     // entries per thread: kBalTaskMax unless that leaves fewer than ~2 waves per SIMD
     uint32_t tsize = kBalTaskMax;
     while (tsize > 4 && (uint64_t)n * W / tsize < kMsmMinThreads) tsize >>= 1;
-    launch(c, ZK_K_MSM, 12.0 * nb, 0, k_bal_counts, blocks_for(nb), (const uint32_t*)dptr<uint32_t>(cnt), nb, tsize,
+    launch(c, ZK_K_MSM, 12.0 * nb, 0, k_bal_counts, blocks1_for(nb), (const uint32_t*)dptr<uint32_t>(cnt), nb, tsize,
            pbal);
     HIPCK(hipMemsetAsync(pbal + nb, 0, 4, c->stream));
     scan_u32(c, pbal, nb + 1);
@@ -252,11 +252,11 @@ std::vector<G1J> msm_window_sums(zk_ctx* c, const G1A* bases, const Fe* scalars,
     DevBuf& pb = c->msm[18];
     pb.ensure(std::max<uint64_t>(1, sizes[1]) * sizeof(G1XYZZ));
     G1XYZZ* parts = dptr<G1XYZZ>(pb);
-    launch(c, ZK_K_MSM, 0, 0, k_bal_empty, blocks_for(nb), (const uint32_t*)dptr<uint32_t>(cnt), nb,
+    launch(c, ZK_K_MSM, 0, 0, k_bal_empty, blocks1_for(nb), (const uint32_t*)dptr<uint32_t>(cnt), nb,
            (const uint32_t*)pbal, parts);
     const uint64_t ntask = ((uint64_t)sizes[0] + tsize - 1) / tsize;
     if (ntask)
-      launch(c, ZK_K_MSM, 0, 0, k_seg_sum_bal, blocks_for(ntask), bases, n, (const uint32_t*)dptr<uint32_t>(ord),
+      launch(c, ZK_K_MSM, 0, 0, k_seg_sum_bal, blocks1_for(ntask), bases, n, (const uint32_t*)dptr<uint32_t>(ord),
              (const uint32_t*)dptr<uint32_t>(cnt), nb, sizes[0], tsize, (const uint32_t*)pbal, (uint64_t)sizes[1],
              parts);
     uint32_t ptask = kSegTask;  // partials per thread: fewer for small MSMs (serial chains)
@@ -271,7 +271,7 @@ std::vector<G1J> msm_window_sums(zk_ctx* c, const G1A* bases, const Fe* scalars,
   const uint32_t chunks = (1u << bb) / bchunk;
   DevBuf& chb = c->msm[13];
   chb.ensure((size_t)Wt * (chunks + 1) * sizeof(G1J));
-  launch(c, ZK_K_MSM, 0, 0, k_window_chunks, blocks_for((uint64_t)Wt * (chunks + 1)), (const G1J*)buckets, bb, Wt,
+  launch(c, ZK_K_MSM, 0, 0, k_window_chunks, blocks1_for((uint64_t)Wt * (chunks + 1)), (const G1J*)buckets, bb, Wt,
          bchunk, dptr<G1J>(chb));
   // the W window sums: equal segments of chunks + 1 points, reduced in levels
   // of msm_win_task points per thread (short tasks keep every level parallel;
@@ -285,7 +285,7 @@ std::vector<G1J> msm_window_sums(zk_ctx* c, const G1A* bases, const Fe* scalars,
       const uint32_t olen = (len + task - 1) / task;
       DevBuf& ob = c->msm[5 + flip];
       ob.ensure((size_t)Wt * olen * sizeof(G1J));
-      launch(c, ZK_K_MSM, 0, 0, k_sum_uniform, blocks_for((uint64_t)Wt * olen), ws, len, Wt, task, dptr<G1J>(ob));
+      launch(c, ZK_K_MSM, 0, 0, k_sum_uniform, blocks1_for((uint64_t)Wt * olen), ws, len, Wt, task, dptr<G1J>(ob));
       ws = dptr<G1J>(ob);
       len = olen;
       flip ^= 1;
@@ -387,7 +387,7 @@ const G1A* g1_fixed_table16(zk_ctx* c) {
   jac.b.ensure(n * sizeof(G1J));
   launch(c, ZK_K_MSM, 0, 0, k_table16, grid_for(c, n, k_table16), t8, dptr<G1J>(jac.b));
   c->g1_table16.ensure(n * sizeof(G1A));
-  launch(c, ZK_K_MSM, 240.0 * n, 0, k_batch_normalize, blocks_for((n + kBatchNorm - 1) / kBatchNorm),
+  launch(c, ZK_K_MSM, 240.0 * n, 0, k_batch_normalize, blocks1_for((n + kBatchNorm - 1) / kBatchNorm),
          (const G1J*)dptr<G1J>(jac.b), n, kBatchNorm, dptr<G1A>(c->g1_table16));
   sync(c);
   return dptr<G1A>(c->g1_table16);
@@ -426,7 +426,7 @@ const G1A* g1_fixed_table20(zk_ctx* c) {
   DevBuf t20;  // owned by the cache once built
   t20.ensure(n * sizeof(G1A));
   try {
-    launch(c, ZK_K_MSM, 240.0 * n, 0, k_batch_normalize, blocks_for((n + kBatchNorm - 1) / kBatchNorm),
+    launch(c, ZK_K_MSM, 240.0 * n, 0, k_batch_normalize, blocks1_for((n + kBatchNorm - 1) / kBatchNorm),
            (const G1J*)dptr<G1J>(jac.b), n, kBatchNorm, dptr<G1A>(t20));
     sync(c);
   } catch (...) {
@@ -710,10 +710,7 @@ int zk_kzg_setup(zk_ctx* c, zk_repr repr, const zk_fe* taus, uint32_t nvars, zk_
     launch(c, ZK_K_MSM, 32.0 * N, (double)N * nvars, zk::k_eq_scalars<Fr381>, grid_for(c, N, zk::k_eq_scalars<Fr381>),
            (const Fe*)tb.p, nvars, N, reinterpret_cast<Fe*>(sc.p));
     // the Jacobian points of every level (released after the normalisation)
-    struct Scoped {
-      DevBuf b;
-      ~Scoped() { b.release(); }
-    } jac;
+    ScopedBuf jac;
     jac.b.ensure(total * sizeof(G1J));
     G1J* J = dptr<G1J>(jac.b);
     if (big)
@@ -744,7 +741,7 @@ int zk_kzg_setup(zk_ctx* c, zk_repr repr, const zk_fe* taus, uint32_t nvars, zk_
     k->basis.ensure(total * sizeof(G1A));
     uint32_t nbatch = zk::kBatchNorm;  // (points per inversion: fewer for small setups, whose time is the chain)
     while (nbatch > 1 && total / nbatch < kMsmMinThreads) nbatch >>= 1;
-    launch(c, ZK_K_MSM, 240.0 * total, 0, zk::k_batch_normalize, blocks_for((total + nbatch - 1) / nbatch),
+    launch(c, ZK_K_MSM, 240.0 * total, 0, zk::k_batch_normalize, blocks1_for((total + nbatch - 1) / nbatch),
            (const G1J*)J, total, nbatch, dptr<G1A>(k->basis));
     sync(c);
     *out = k.release();

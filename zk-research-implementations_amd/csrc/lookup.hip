@@ -24,28 +24,11 @@ struct zk_lookup {
 namespace {
 using Fr381 = zk::Bls12_381Fr;
 
-void check_repr(zk_repr repr) { require(repr == ZK_REPR_CANONICAL || repr == ZK_REPR_MONTGOMERY, "unknown repr"); }
-
-// an inner C-ABI call's failure, passed on with its message
-void pass_on(int rc) {
-  if (rc != ZK_OK) {
-    const std::string msg = g_last_error;
-    fail(rc, msg);
-  }
-}
-
-void plan_check(int rc, const char* err) {
-  if (rc != zkl::L_OK) fail(rc == zkl::L_EUNSUPPORTED ? ZK_EUNSUPPORTED : ZK_EINVAL, err);
-}
+constexpr auto plan_check = plan_check_with<zkl::L_OK, zkl::L_EUNSUPPORTED>;
 
 void lookup_release(zk_lookup* lk) {
   for (DevBuf* b : {&lk->d_tm, &lk->d_slots, &lk->d_counts, &lk->tabs}) b->release();
   delete lk;
-}
-
-bool overlap(const void* a, const void* b, uint64_t bytes) {
-  const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-  return x < y + bytes && y < x + bytes;
 }
 
 // counts zeroed, one probe per entry, the counters written out as elements

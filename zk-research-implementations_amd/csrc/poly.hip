@@ -11,9 +11,6 @@
 using namespace zkh;
 
 namespace {
-void check_repr(zk_repr repr) {
-  require(repr == ZK_REPR_CANONICAL || repr == ZK_REPR_MONTGOMERY, "unknown representation");
-}
 void check_field(zk_field field) {
   require(field == ZK_BN254_FR || field == ZK_BN254_FQ || field == ZK_BLS12_381_FR, "unknown field");
 }
@@ -102,7 +99,7 @@ int zk_poly_evaluate(zk_ctx* c, zk_field field, zk_repr repr, const zk_fe* coeff
                      uint64_t npoints, zk_fe* out) {
   return guarded([&] {
     require((coeffs || ncoeffs == 0) && (npoints == 0 || (xs && out)), "null argument");
-    check_repr(repr);
+    check_repr(repr, "unknown representation");
     check_field(field);
     check_eval_size(ncoeffs, npoints);
     require(c != nullptr, "null context");
@@ -163,7 +160,7 @@ int zk_poly_interpolate(zk_ctx* c, zk_field field, zk_repr repr, const zk_fe* xs
                         zk_fe* out_coeffs, uint64_t cap, uint64_t* out_ncoeffs) {
   return guarded([&] {
     require(out_ncoeffs != nullptr && (n == 0 || (xs && ys && out_coeffs)), "null argument");
-    check_repr(repr);
+    check_repr(repr, "unknown representation");
     check_field(field);
     if (n > kPolyInterpMax) fail(ZK_EUNSUPPORTED, "interpolation of more than 2^16 points is not supported");
     require(cap >= n, "the output buffer is shorter than the number of points");

@@ -10,13 +10,11 @@
 using namespace zkh;
 
 namespace {
-// One grouping of the entries on the device (r1cs_plan.hpp R1csGroup).
+// One grouping of the entries on the device (r1cs_plan.hpp R1csGroup): the
+// shared layout and the entries' values in its order.
 struct DevGroup {
-  DevBuf other, vals, chunks, split;
-  uint32_t nchunks = 0, nsingle = 0, nsplit = 0, nslots = 0;
-  void release() {
-    for (DevBuf* b : {&other, &vals, &chunks, &split}) b->release();
-  }
+  DevCsr csr;
+  DevBuf vals;
 };
 }  // namespace
 
@@ -35,46 +33,23 @@ struct zk_r1cs {
 };
 
 namespace {
-void check_repr(zk_repr repr) { require(repr == ZK_REPR_CANONICAL || repr == ZK_REPR_MONTGOMERY, "unknown repr"); }
-
-// an inner C-ABI call's failure, passed on with its message
-void pass_on(int rc) {
-  if (rc != ZK_OK) {
-    const std::string msg = g_last_error;
-    fail(rc, msg);
-  }
-}
-
-void plan_check(int rc, const char* err) {
-  if (rc != zkr::R_OK) fail(rc == zkr::R_EUNSUPPORTED ? ZK_EUNSUPPORTED : ZK_EINVAL, err);
-}
+constexpr auto plan_check = plan_check_with<zkr::R_OK, zkr::R_EUNSUPPORTED>;
 
 void r1cs_release(zk_r1cs* r) {
-  r->by_row.release();
-  r->by_col.release();
+  for (DevGroup* g : {&r->by_row, &r->by_col}) {
+    g->csr.release();
+    g->vals.release();
+  }
   for (DevBuf* b : {&r->tabs, &r->slots, &r->dot}) b->release();
   delete r;
 }
 
-uint32_t blocks_for(uint64_t n) { return (uint32_t)((n + zk::kBlock - 1) / zk::kBlock); }
-
-template <class T>
-void to_device(DevBuf& b, const std::vector<T>& v) {
-  b.ensure(std::max<size_t>(v.size() * sizeof(T), 16));
-  if (!v.empty()) HIPCK(hipMemcpy(b.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-}
 void group_to_device(DevGroup& d, const zk_r1cs* r, bool by_row) {
   const zkr::R1csGroup g = zkr::r1cs_group(r->sh, r->rows.data(), r->cols.data(), by_row);
   std::vector<Fe> vals(g.other.size());
   for (size_t i = 0; i < vals.size(); ++i) vals[i] = r->vm[g.csr.gate[i]];
-  to_device(d.other, g.other);
+  d.csr.load(g.csr, g.other);
   to_device(d.vals, vals);
-  to_device(d.chunks, g.csr.chunks);
-  to_device(d.split, g.csr.split);
-  d.nchunks = (uint32_t)g.csr.chunks.size();
-  d.nsingle = g.csr.nsingle;
-  d.nsplit = (uint32_t)g.csr.split.size();
-  d.nslots = d.nchunks - d.nsingle;
 }
 
 // The handle's tables, in elements: six of 2^sx for sum-check 1, then of 2^sy
@@ -99,9 +74,10 @@ Tabs tabs_of(zk_r1cs* r) {
 // One pass over a grouping into `nout` rows of NC columns: zero, the chunks,
 // then the split rows' slots added in.
 template <class F, int NC>
-void gather_pass(zk_r1cs* r, const DevGroup& g, const Fe* x, uint32_t nout, const Fe& rho, const Fe& rho2, Fe* o0,
+void gather_pass(zk_r1cs* r, const DevGroup& dg, const Fe* x, uint32_t nout, const Fe& rho, const Fe& rho2, Fe* o0,
                  Fe* o1, Fe* o2) {
   zk_ctx* c = r->c;
+  const DevCsr& g = dg.csr;
   const double n = (double)r->sh.total();
   Fe* p0 = r->slots.fe();
   Fe* p1 = p0 + r->nslots;
@@ -109,27 +85,13 @@ void gather_pass(zk_r1cs* r, const DevGroup& g, const Fe* x, uint32_t nout, cons
   launch(c, ZK_K_LAYER, 32.0 * NC * nout, 0.0, zk::k_r1cs_zero<F, NC>, blocks_for(nout), nout, o0, o1, o2);
   if (g.nchunks)
     launch(c, ZK_K_LAYER, 68.0 * n + (12.0 + 32.0 * NC) * g.nchunks, n, zk::k_r1cs_gather<F, NC>, blocks_for(g.nchunks),
-           x, (const Fe*)g.vals.fe(), reinterpret_cast<const uint32_t*>(g.other.p),
+           x, (const Fe*)dg.vals.fe(), reinterpret_cast<const uint32_t*>(g.other.p),
            reinterpret_cast<const zk::WiredChunk*>(g.chunks.p), g.nchunks, g.nsingle, rho, rho2, o0, o1, o2, p0, p1,
            p2);
   if (g.nsplit)
     launch(c, ZK_K_LAYER, 32.0 * NC * (g.nslots + g.nsplit), 0.0, zk::k_r1cs_combine<F, NC>, g.nsplit,
            reinterpret_cast<const zk::WiredChunk*>(g.split.p), (const Fe*)p0, (const Fe*)p1, (const Fe*)p2, o0, o1,
            o2);
-}
-
-// sum_j w[j] e[j] over n entries on the device (k_wired_dot), the blocks' parts added here
-template <class F>
-Fe dot_device(zk_r1cs* r, const Fe* w, const Fe* e, uint64_t n) {
-  zk_ctx* c = r->c;
-  const uint32_t grid = (uint32_t)std::min<uint64_t>(blocks_for(n), 64);
-  launch(c, ZK_K_LAYER, 64.0 * n, (double)n, zk::k_wired_dot<F>, grid, w, e, n, r->dot.fe());
-  Fe part[64];
-  HIPCK(hipMemcpyAsync(part, r->dot.fe(), grid * sizeof(Fe), hipMemcpyDeviceToHost, c->stream));
-  sync(c);
-  Fe s = zk::fe_zero<F>();
-  for (uint32_t i = 0; i < grid; ++i) s = zk::hfe_add<F>(s, part[i]);
-  return s;
 }
 
 // eq(pt[0..n), .) into d_out through the public builder (Montgomery scalars)
@@ -147,7 +109,7 @@ void matrix_evals_device(zk_r1cs* r, const Fe* rx, const Fe* ry, Fe (&out)[3]) {
   const Fe zero = zk::fe_zero<F>();
   gather_pass<F, 3>(r, r->by_col, t.t1(0), (uint32_t)t.Y, zero, zero, t.col(0), t.col(1), t.col(2));
   eq_table<F>(r, ry, r->sh.sy, t.e());
-  for (int k = 0; k < 3; ++k) out[k] = dot_device<F>(r, t.col(k), t.e(), t.Y);
+  for (int k = 0; k < 3; ++k) out[k] = dot_device<F>(r->c, r->dot, t.col(k), t.e(), t.Y);
 }
 
 struct ProveArgs {
@@ -260,7 +222,7 @@ void prove_device(zk_r1cs* r, zk_repr repr, const Fe* d_w, const ProveArgs& a) {
     sync(c);
   } else {
     eq_table<F>(r, ry + 1, sy - 1, t.e());
-    p.vw = dot_device<F>(r, d_w, t.e(), H);
+    p.vw = dot_device<F>(r->c, r->dot, d_w, t.e(), H);
   }
   absorb<F>(&tr, &p.vw, 1);
   std::vector<zk_g1> opening;
@@ -318,7 +280,7 @@ int zk_r1cs_new(zk_ctx* c, zk_field field, zk_repr repr, uint32_t nrows, uint32_
         bind(c);
         group_to_device(r->by_row, r, true);
         group_to_device(r->by_col, r, false);
-        r->nslots = std::max(r->by_row.nslots, r->by_col.nslots);
+        r->nslots = std::max(r->by_row.csr.nslots, r->by_col.csr.nslots);
       } catch (...) {
         r1cs_release(r);
         throw;

@@ -463,33 +463,13 @@ int zk_gkr_sumcheck_verify(zk_field field, zk_repr repr, const zk_fe* coeffs, co
       using F = decltype(f);
       using namespace zk;
       Fe claim = in_mont<F>(repr, *claimed_sum);
-      const Fe zero = fe_zero<F>(), one = fe_one<F>();
-      for (uint32_t k = 0; k < nrounds; ++k) {
-        require(ncoeffs[k] <= 3, "round polynomial has more than 3 coefficients");
-        Fe cf[3];
-        const int m = ncoeffs[k];
-        for (int i = 0; i < m; ++i) cf[i] = in_mont<F>(repr, coeffs[3 * k + i]);
-        // UnivariatePoly::evaluate (univariate_polynomial_dense.rs:20-26)
-        auto eval = [&](const Fe& x) {
-          Fe s = zero, xp = one;
-          for (int i = 0; i < m; ++i) {
-            s = fe_add<F>(s, fe_mul<F>(cf[i], xp));
-            xp = fe_mul<F>(xp, x);
-          }
-          return s;
-        };
-        if (!fe_eq<F>(fe_add<F>(eval(zero), eval(one)), claim)) {  // :128-134
-          *out_verified = 0;
-          *out_final_claimed_sum = out_repr<F>(repr, zero);
-          out_challenges[0] = out_repr<F>(repr, zero);
-          return;
-        }
-        absorb<F>(transcript, cf, (size_t)m);
-        const Fe r = challenge<F>(transcript);
-        out_challenges[k] = out_repr<F>(repr, r);
-        claim = eval(r);
+      std::vector<Fe> chal;
+      *out_verified = gkr_verify_rounds<F>(repr, coeffs, ncoeffs, 0, nrounds, transcript, claim, chal);
+      for (size_t k = 0; k < chal.size(); ++k) out_challenges[k] = out_repr<F>(repr, chal[k]);
+      if (!*out_verified) {  // :128-134
+        claim = fe_zero<F>();
+        out_challenges[0] = out_repr<F>(repr, claim);
       }
-      *out_verified = 1;
       *out_final_claimed_sum = out_repr<F>(repr, claim);
     });
   });
